@@ -13,7 +13,7 @@ every N (default ``--shard users``: weak scaling over test-user blocks, rank r
 scores test users [10r, 10r+10) of a 500 x 10N dataset over all songs, an
 exact partition of the model's pairs, no data-path collective — C2 is one
 ~12 us latency-bound launch, SURVEY.md §8e: "C2 is too small to scale"). The
-C2 line carries a nested ``north_star`` block at every N, including 1: C4
+C2 line of a ``--full`` run carries a nested ``north_star`` block at every N, including 1: C4
 (1M train / 10k test / 384,546 songs, top-10) in the north star's layout —
 N song shards x 1 user block (sharding.ShardScorer, G_s = N: each rank the
 same whole number of wide tiles, its own co-listening index over its songs;
@@ -25,6 +25,17 @@ two-hop bytes) and, at N = 1, the CPU two-hop baseline.
 Rank 0 builds C4 once and the node's other ranks load its arrays.
 ``--shard songs`` / ``--shard 2d --song-groups G_s`` run those layouts as the
 main line (``--config c4`` / ``c5`` for the full-scale configs).
+
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline
+needs: set-up, W warm-up steps, the K timed steps, the result line (its
+roofline block from the byte model and the engine-stream event window of the
+same K steps). ``--full`` adds everything that takes runs of its own: the
+``north_star`` block, the CPU baselines, the end-to-end timing and the
+threshold-mAP companions (``--no-north-star`` / ``--no-cpu-baseline`` /
+``--no-e2e`` switch each off again). ``--dump-outputs DIR`` writes the last
+timed step's outputs (dense scores, top-k lists) as ``DIR/<name>.npy``, all
+values finite (the dense model's NaN marks go to ``<name>_nan.npy``); the
+inputs are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the byte model.
 """
@@ -309,8 +320,12 @@ def run_c5(args, world: int, rank: int, local: int) -> None:
     if _pg():
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     elapsed = float(t_max.item())
+    if args.dump_outputs:  # the last timed step's five dense models (a fixed sample each) and their mAPs
+        outs = dict(models)
+        outs["threshold_mAP"] = np.array([maps[n] for n in ("ubm", "ibm", "lcm", "am", "scm")], dtype=np.float64)
+        dump_outputs(args.dump_outputs, outs, world, rank)
     songs = None
-    if world == 1:
+    if world == 1 and args.full:
         songs, _sc, _k = ens.topk(models["lcm"])
     if rank == 0:
         pairs = full.n_pairs()
@@ -708,6 +723,48 @@ def end_to_end_bulk(trip, model: str, reps: int = 2, k: int = 10):
                     f"mr_run + D2H of the top-{k} lists; files written beforehand in {write_s:.1f} s (untimed)"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: array bytes of one run together (< 64 MB with the headers)
+
+
+def _dump_sample(a, max_elems: int):
+    """`a` (numpy array or torch tensor) as a numpy array of at most max_elems
+    elements: the whole array, or a fixed sample of it (seed 0: the same flat
+    positions in every run, in ascending order)."""
+    n = int(a.numel()) if isinstance(a, torch.Tensor) else int(a.size)
+    if n > max_elems:
+        idx = np.sort(np.random.default_rng(0).integers(0, n, size=max_elems))
+        a = a.reshape(-1)[torch.from_numpy(idx).to(a.device) if isinstance(a, torch.Tensor) else idx]
+    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def dump_outputs(out_dir: str, arrays: dict, world: int = 1, rank: int = 0) -> None:
+    """--dump-outputs: the last timed step's outputs as <out_dir>/<name>.npy
+    (rank r > 0 of a multi-GPU run: <name>_rank<r>.npy), every value finite.
+    Floating-point arrays as float32 / float64; a dense model marks the
+    (user, heard song) positions, which are no pairs, with NaN: those are
+    written as 0 in <name>.npy and as 1 in a float32 mask <name>_nan.npy (0
+    elsewhere; the file exists only if the array has such positions). int32
+    song ids as float64 (exact); int64 fixed-point keys as two float64 arrays,
+    <name>_hi (key >> 32) and <name>_lo (the low 32 bits), both exact. Each
+    array larger than its share of the budget (64 MB in all, a mask counted)
+    is written as a fixed sample (_dump_sample)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_array = DUMP_BUDGET_BYTES // (8 * 2 * len(arrays))  # two files per array at most, 8 B per element
+    sfx = f"_rank{rank}" if world > 1 and rank else ""
+    for name, a in arrays.items():
+        a = _dump_sample(a, per_array)
+        if a.dtype == np.int64:
+            np.save(os.path.join(out_dir, f"{name}_hi{sfx}.npy"), (a >> 32).astype(np.float64))
+            np.save(os.path.join(out_dir, f"{name}_lo{sfx}.npy"), (a & 0xFFFFFFFF).astype(np.float64))
+            continue
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        bad = ~np.isfinite(a)
+        if bad.any():
+            np.save(os.path.join(out_dir, f"{name}_nan{sfx}.npy"), bad.astype(np.float32))
+            a = np.where(bad, a.dtype.type(0), a)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -751,7 +808,19 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per score-kernel launch measured by rocprofv3 PMC (profiles/)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the nested north_star block (C4), the "
+                         "CPU baselines, the end-to-end timing and the threshold-mAP quality companions "
+                         "(each still switched off by its own --no-... option); a plain run sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (dense scores, top-k lists) as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline figure only
+        args.no_north_star = args.no_cpu_baseline = args.no_e2e = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -900,6 +969,17 @@ def main() -> None:
     else:
         elapsed_max, pairs_all = elapsed, pairs_total_rank
 
+    if args.dump_outputs:  # what the last timed step left in the engine's output buffers
+        if args.shard == "users" and not bulk:
+            o_songs, o_scores, o_keys = eng.topk()
+            outs = {"topk_songs": o_songs, "topk_scores": o_scores, "topk_keys": o_keys}
+        else:  # this rank's user block, merged over its song shards
+            o_songs, o_keys = scorer.topk()
+            outs = {"topk_songs": o_songs, "topk_keys": o_keys}
+        if dense_out:
+            outs["dense"] = eng.dense()
+        dump_outputs(args.dump_outputs, outs, world, rank)
+
     ns = None
     if args.config == "c2" and not args.no_north_star:  # every rank (collectives inside)
         ns = north_star(args, world, rank, local)
@@ -940,7 +1020,8 @@ def main() -> None:
         if args.shard == "users" and not bulk:
             songs, _sc, _k = eng.topk()
             map10 = evaluation.map_at_k(songs, ds, 10)
-            ref_map = evaluation.threshold_map(eng.dense().astype(np.float64), ds) if dense_out else None
+            ref_map = (evaluation.threshold_map(eng.dense().astype(np.float64), ds)
+                       if dense_out and args.full else None)
         else:
             s_, _k = scorer.topk()
             map10 = evaluation.map_at_k(s_, ds, 10)  # this rank's user block

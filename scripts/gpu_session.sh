@@ -72,13 +72,13 @@ case ",$STEPS," in *,ab,*)
 esac
 case ",$STEPS," in *,stamps,*) run stamps 300 python scripts/stamps.py ${STAMPS:-c2 ibm 0 auto} ;; esac
 case ",$STEPS," in *,ingest,*) MR_INGEST_TRACE=1 MR_LOAD_TRACE=1 run ingest_c4 900 python -u scripts/ingest_probe.py --config c4 --load --reps 3 --out "$OUT/ingest_c4.json" ;; esac
-case ",$STEPS," in *,bench,*) run bench 600 python bench.py ;; esac
+case ",$STEPS," in *,bench,*) run bench 600 python bench.py --full ;; esac
 case ",$STEPS," in *,prof,*)
   export TMPDIR=/tmp
-  run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --no-cpu-baseline --steps 200 ;;
+  run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 200 ;;
 esac
-case ",$STEPS," in *,c4,*) run bench_c4 900 python -u bench.py --config c4 --steps 5 --warmup 2 ;; esac
-case ",$STEPS," in *,c5,*) run bench_c5 900 python -u bench.py --config c5 --steps 3 --warmup 1 ;; esac
+case ",$STEPS," in *,c4,*) run bench_c4 900 python -u bench.py --full --config c4 --steps 5 --warmup 2 ;; esac
+case ",$STEPS," in *,c5,*) run bench_c5 900 python -u bench.py --full --config c5 --steps 3 --warmup 1 ;; esac
 # C5 per-model layouts (sharding.EnsembleScorer): every rank's slice on this GPU (C5N="8 4 2")
 case ",$STEPS," in *,c5models,*) run c5_models 900 python -u scripts/c5_layout_probe.py ${C5N:-8} ;; esac
 case ",$STEPS," in *,profc5models,*)
@@ -189,13 +189,13 @@ for n in 2 4 8; do
   case ",$STEPS," in *,rehearse$n,*)
     MR_BENCH_BACKEND=gloo MR_BENCH_DEVICE=0 PYTHONUNBUFFERED=1 run rehearse_n$n 900 python -m torch.distributed.run \
       --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --gpus $n \
-      --steps 50 --warmup 5 --no-cpu-baseline ;;
+      --full --steps 50 --warmup 5 --no-cpu-baseline ;;
   esac
 done
-case ",$STEPS," in *,c3,*) run bench_c3 600 python bench.py --config c3 --no-cpu-baseline --steps 20 --warmup 3 ;; esac
+case ",$STEPS," in *,c3,*) run bench_c3 600 python bench.py --full --config c3 --no-cpu-baseline --steps 20 --warmup 3 ;; esac
 case ",$STEPS," in *,profc3,*)
   export TMPDIR=/tmp
-  run prof_c3 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c3" -o bench -- python3 "$ROOT/bench.py" --config c3 --no-cpu-baseline --steps 20 --warmup 3 ;;
+  run prof_c3 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c3" -o bench -- python3 "$ROOT/bench.py" --full --config c3 --no-cpu-baseline --steps 20 --warmup 3 ;;
 esac
 # PMC of one C4 neighbour batch (scripts/c4_probe.py): fetched bytes, then
 # instruction / wave-cycle counters, each pass its own run

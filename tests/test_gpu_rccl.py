@@ -144,7 +144,7 @@ def test_bench_one_rank_rccl_rehearsal(tmp_path):
     barriers, MAX/SUM all-reduces and the forced all-gather exchange, all over
     RCCL (the north star on the 10k/1k C3 shape to keep the test short)."""
     env = dict(os.environ, MR_BENCH_PG="1", TMPDIR=str(tmp_path), PYTHONUNBUFFERED="1")
-    p = _torchrun(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-e2e",
+    p = _torchrun(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-e2e",
                    "--ns-config", "c3", "--ns-steps", "3", "--ns-warmup", "1"], env)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
