@@ -417,6 +417,42 @@ int mr_eval_class_counts_device(mr_ctx* ctx, int32_t n_models, const void* const
 int mr_eval_map_counts_device(mr_ctx* ctx, int32_t n_models, int32_t n_classes, const int32_t* class_pos,
                               const int32_t* counts, int32_t n_label_songs, double* maps_out, int32_t n_thresholds);
 
+/* ---- parameter sweep: the threshold mAP of one combination kind at n_params values ----
+ * (the experiment of the reference's README, "Some notes about combination
+ * models and future experiments": which alpha / percentage / probability to
+ * use). No combined model is materialised: out_j(u, s), exactly the value
+ * mr_combine_device(kind, params[j], seed, ...) would store, is formed in
+ * registers from ubm and ibm (device pointers, as above) — once for the
+ * extremes of all n_params outputs, and per group of MR_SWEEP_G parameters for
+ * the counts. The stochastic draw of a pair is shared by every parameter.
+ * params: host, 1..MR_SWEEP_MAX_PARAMS values in any order, repeats allowed
+ * (each in [0, 1] unless the kind is linear). All three are synchronous.
+ * mr_sweep_minmax_device: mn[j] / mx[j] = min / max of out_j over the
+ *   context's pairs (+inf / -inf when it holds none).
+ * mr_sweep_class_counts_device: mr_eval_class_counts_device with one "model"
+ *   per parameter — counts (DEVICE, n_params x 2 x n_classes x n_thresholds
+ *   int32) laid out by the shared class list, mn / mx the GLOBAL extremes per
+ *   parameter (mn > mx: that parameter's counts are 0) — so a SUM all-reduce
+ *   and mr_eval_map_counts_device(ctx, n_params, ...) give every mAP.
+ * mr_sweep_map_device: the three passes and the fold for a context that holds
+ *   the whole model (pos: host [>= song_hi], global label counts); maps_out[j]
+ *   is bit-equal to mr_combine_device + mr_eval_minmax_device +
+ *   mr_eval_map_device for params[j]; minmax_out (may be NULL): [n_params][2].
+ *   MR_E_INVALID, naming the parameter, when an output has no pair (MR:524). */
+#define MR_SWEEP_MAX_PARAMS 64
+int mr_sweep_minmax_device(mr_ctx* ctx, int kind, int32_t n_params, const double* params, uint64_t seed,
+                           int64_t pair_base, int64_t n_pairs, const void* ubm, const void* ibm, double* mn,
+                           double* mx);
+int mr_sweep_class_counts_device(mr_ctx* ctx, int kind, int32_t n_params, const double* params, uint64_t seed,
+                                 int64_t pair_base, int64_t n_pairs, const void* ubm, const void* ibm,
+                                 const double* mn, const double* mx, const int64_t* lab_off,
+                                 const int32_t* lab_songs, int32_t n_classes, const int32_t* classes,
+                                 int32_t* counts, int32_t n_thresholds);
+int mr_sweep_map_device(mr_ctx* ctx, int kind, int32_t n_params, const double* params, uint64_t seed,
+                        int64_t pair_base, int64_t n_pairs, const void* ubm, const void* ibm, const int64_t* lab_off,
+                        const int32_t* lab_songs, const int32_t* pos, int32_t n_label_songs, double* maps_out,
+                        double* minmax_out, int32_t n_thresholds);
+
 /* Kernel timing of mr_run calls made with opt.time_kernels = 1: per kernel
  * (0 = separate stage-1 kernel — neighbour lists —, 1 = the
  * scoring kernels — stage 2, fused stage 1, the in-launch top-k merge, the wide

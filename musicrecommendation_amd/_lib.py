@@ -118,6 +118,7 @@ class MrCoocBytes(ctypes.Structure):
 MR_COMB_LINEAR = 0
 MR_COMB_AGGREGATION = 1
 MR_COMB_STOCHASTIC = 2
+MR_SWEEP_MAX_PARAMS = 64
 
 
 class EngineError(RuntimeError):
@@ -182,6 +183,13 @@ SIGNATURES = {
                                             c_int32, c_void_p, c_void_p, c_int32]),
     "mr_eval_map_counts_device": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                           c_int32]),
+    "mr_sweep_minmax_device": (c_int, [c_void_p, c_int, c_int32, c_void_p, ctypes.c_uint64, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "mr_sweep_class_counts_device": (c_int, [c_void_p, c_int, c_int32, c_void_p, ctypes.c_uint64, c_int64, c_int64,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                             c_void_p, c_void_p, c_int32]),
+    "mr_sweep_map_device": (c_int, [c_void_p, c_int, c_int32, c_void_p, ctypes.c_uint64, c_int64, c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32]),
     "mr_last_error": (c_char_p, []),
     "mr_corpus_from_tsv": (c_int, [c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
     "mr_corpus_dataset": (c_int, [c_void_p, POINTER(MrDataset)]),

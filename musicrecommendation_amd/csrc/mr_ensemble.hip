@@ -429,6 +429,23 @@ struct Tmp {  // scratch device buffer of one call, stream-ordered (pool allocat
   ~Tmp() { if (p) (void)hipFreeAsync(p, st); }
 };
 
+// The label CSR of the context's test users as (user, song) pairs, one per
+// label (at least one slot, so the staging buffers are never empty).
+int label_pairs(int n_te, const int64_t* lab_off, const int32_t* lab_songs, std::vector<int32_t>& lu,
+                std::vector<int32_t>& ls) {
+  const long long n_lab = lab_off[n_te];
+  if (n_lab > 0 && !lab_songs) return fail(MR_E_INVALID, "null label songs");
+  lu.assign((size_t)std::max<long long>(1, n_lab), 0);
+  ls.assign((size_t)std::max<long long>(1, n_lab), 0);
+  for (int u = 0; u < n_te; ++u)
+    for (int64_t j = lab_off[u]; j < lab_off[u + 1]; ++j) {
+      if (j < 0 || j >= n_lab || lab_off[u + 1] < lab_off[u]) return fail(MR_E_INVALID, "bad label CSR");
+      lu[j] = u;
+      ls[j] = lab_songs[j];
+    }
+  return MR_OK;
+}
+
 // pred / tp counts of the shard into the device buffers d_pred / d_tp
 // ([width][n_thr], stream-ordered on the context stream; the caller frees
 // them), for n_models dense models in turn: the labels are staged once, and
@@ -447,15 +464,9 @@ int eval_counts(mr_ctx* ctx, int n_models, const void* const* dense, const doubl
   if (rc) return rc;
   MR_HIP(hipSetDevice(v.device));
   const int width = v.song_hi - v.song_lo, n_te = v.n_test_users;
+  std::vector<int32_t> lu, ls;
+  if ((rc = label_pairs(n_te, lab_off, lab_songs, lu, ls))) return rc;
   const long long n_lab = lab_off[n_te];
-  if (n_lab > 0 && !lab_songs) return fail(MR_E_INVALID, "null label songs");
-  std::vector<int32_t> lu((size_t)std::max<long long>(1, n_lab)), ls((size_t)std::max<long long>(1, n_lab));
-  for (int u = 0; u < n_te; ++u)
-    for (int64_t j = lab_off[u]; j < lab_off[u + 1]; ++j) {
-      if (j < 0 || j >= n_lab || lab_off[u + 1] < lab_off[u]) return fail(MR_E_INVALID, "bad label CSR");
-      lu[j] = u;
-      ls[j] = lab_songs[j];
-    }
   hipStream_t st = (hipStream_t)v.stream;
   Tmp<int> d_lu, d_ls;
   d_pred.st = d_tp.st = d_lu.st = d_ls.st = st;
@@ -500,6 +511,492 @@ int eval_counts(mr_ctx* ctx, int n_models, const void* const* dense, const doubl
     if ((rc = after(i))) return rc;
   }
   // the label staging is freed in stream order after these kernels (Tmp)
+  return MR_OK;
+}
+
+// ---- parameter sweep ---------------------------------------------------------
+// The threshold mAP of one combination kind at P parameter values without
+// materialising a combined model: out_j(u, s) is formed in registers from ubm
+// and ibm with k_combine's expressions (same element type, same fp64
+// operations), three times — for the extremes, the predicted counts and the
+// true positives. The tail (class block, k_eval_ap, ordered host sum) is the
+// evaluation's own.
+#ifndef MR_SWEEP_G
+#define MR_SWEEP_G 4  // parameters per counting pass: G x n_thr register counters per thread
+#endif
+#ifndef MR_SWEEP_U
+#define MR_SWEEP_U 8  // rows in flight per thread: 2 x 8 loads, k_eval_pred's 16
+#endif
+constexpr int kSweepG = MR_SWEEP_G;
+constexpr int kSweepMax = MR_SWEEP_MAX_PARAMS;
+constexpr int kWave = 64;
+
+struct SweepTab {  // per parameter j, device-resident for the call
+  double p[kSweepMax];        // p_j
+  double q[kSweepMax];        // 1.0 - p_j (the linear weight of ibm, MR:327)
+  long long thr[kSweepMax];   // (long long)(p_j * n_pairs) (aggregation, MR:371)
+  double mn[kSweepMax], mx[kSweepMax];  // global extremes of out_j
+  float xt_f[kSweepMax][kThresholds];   // level_floor per threshold (+inf past n_thr)
+  double xt_d[kSweepMax][kThresholds];
+};
+
+struct SweepParams {
+  int n_te, width, song_lo, n_songs, n_params, n_thr, users_per_block;
+  unsigned long long seed;
+  long long pair_base;
+  const long long* te_off;
+  const int* te_songs;
+  const void* ubm;
+  const void* ibm;
+  const SweepTab* tab;
+  int* pred;  // [G][width][n_thr], the counts of one group of parameters
+  int* tp;
+  const int* lab_u;
+  const int* lab_s;
+  long long n_lab;
+  double* part;  // [blocks][n_params][2]
+};
+
+// first index in te_songs[a, b) (sorted) whose song is >= s
+__device__ __forceinline__ long long first_heard(const int* te_songs, long long a, long long b, int s) {
+  while (a < b) {
+    const long long m = (a + b) >> 1;
+    if (te_songs[m] < s) a = m + 1; else b = m;
+  }
+  return a;
+}
+
+// Index of pair (u, s) as k_combine computes it (pair_base + u * n_s - t0 + s
+// - (j - t0)), j = first index of T(u) = te_songs[.., t1) with a song >= s;
+// -1 for a heard song (no pair, MR:109).
+__device__ __forceinline__ long long sweep_pair(const SweepParams& p, int u, int s, long long j, long long t1) {
+  if (j < t1 && p.te_songs[j] == s) return -1;
+  return p.pair_base + (long long)u * p.n_songs + s - j;
+}
+
+// What selects ibm over ubm for one element, shared by every parameter: the
+// pair index (aggregation) or the pair's uniform draw (stochastic).
+template <int K>
+struct SweepKey { long long v; };
+template <>
+struct SweepKey<MR_COMB_STOCHASTIC> { float v; };
+
+template <int K>
+__device__ __forceinline__ SweepKey<K> sweep_key(const SweepParams& p, long long idx) {
+  SweepKey<K> k;
+  if constexpr (K == MR_COMB_STOCHASTIC) k.v = pair_uniform(p.seed, idx);
+  else k.v = idx;
+  return k;
+}
+
+// out_j of one element: the value k_combine<OutT> stores for param = p_j
+// (a, b = NaN for a heard song of the selecting kinds).
+template <typename OutT, int K>
+__device__ __forceinline__ OutT sweep_out(OutT a, OutT b, SweepKey<K> key, double pj, double qj, long long thr) {
+  if constexpr (K == MR_COMB_LINEAR) return (OutT)((double)a * pj + (double)b * qj);  // MR:327
+  else if constexpr (K == MR_COMB_AGGREGATION) return key.v < thr ? b : a;           // MR:380-381
+  else return (double)key.v < pj ? b : a;                                            // MR:414-415
+}
+
+__device__ __forceinline__ float wave_xor(float x, int m) { return __shfl_xor(x, m, kWave); }
+__device__ __forceinline__ double wave_xor(double x, int m) { return __shfl_xor(x, m, kWave); }
+
+// Extremes pass. A workgroup takes one kThreads * kCombPer song block (as
+// k_combine) and walks the users blockIdx.y, + gridDim.y, ...: the elements of
+// one (user, block) stay in registers while the P outputs are formed from them
+// in turn; each output's min / max (NaN skipped, in the element type) is
+// reduced over the wave and folded into the wave's running pair in LDS (lane 0
+// owns its wave's slots: no barrier inside the loop). The user walk keeps the
+// partials at [blocks][P][2] for a few thousand blocks whatever the user
+// count, and grid-y far below its limit.
+template <typename OutT, int K>
+__global__ __launch_bounds__(kThreads) void k_sweep_minmax(SweepParams p) {
+  __shared__ double sm[kThreads / kWave][kSweepMax][2];
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const SweepTab* __restrict__ tab = p.tab;
+  for (int j = lane; j < p.n_params; j += kWave) {
+    sm[wave][j][0] = INFINITY;
+    sm[wave][j][1] = -INFINITY;
+  }
+  __syncthreads();
+  const int i0 = blockIdx.x * kThreads * kCombPer + threadIdx.x;
+  const int s_blk = p.song_lo + blockIdx.x * kThreads * kCombPer;  // first song of the block
+  for (int u = blockIdx.y; u < p.n_te; u += gridDim.y) {
+    const size_t row = (size_t)u * p.width;
+    const OutT* ubm = reinterpret_cast<const OutT*>(p.ubm) + row;
+    const OutT* ibm = reinterpret_cast<const OutT*>(p.ibm) + row;
+    OutT a4[kCombPer], b4[kCombPer];
+    SweepKey<K> key[kCombPer] = {};
+#pragma unroll
+    for (int r = 0; r < kCombPer; ++r) {  // past the width: NaN, skipped
+      const int i = i0 + r * kThreads;
+      a4[r] = i < p.width ? ubm[i] : (OutT)NAN;
+      b4[r] = i < p.width ? ibm[i] : (OutT)NAN;
+    }
+    if constexpr (K != MR_COMB_LINEAR) {
+      const long long t1 = p.te_off[u + 1];
+      const long long j0 = first_heard(p.te_songs, p.te_off[u], t1, s_blk);  // uniform over the block
+#pragma unroll
+      for (int r = 0; r < kCombPer; ++r) {
+        const int i = i0 + r * kThreads;
+        key[r] = SweepKey<K>{};
+        if (i >= p.width) continue;
+        const int s = p.song_lo + i;
+        long long j = j0;
+        while (j < t1 && p.te_songs[j] < s) ++j;
+        const long long idx = sweep_pair(p, u, s, j, t1);
+        if (idx < 0) a4[r] = b4[r] = (OutT)NAN;
+        key[r] = sweep_key<K>(p, idx);
+      }
+    }
+    for (int j = 0; j < p.n_params; ++j) {
+      const double pj = tab->p[j], qj = tab->q[j];
+      const long long thr = tab->thr[j];
+      OutT mn = (OutT)INFINITY, mx = (OutT)-INFINITY;
+#pragma unroll
+      for (int r = 0; r < kCombPer; ++r) {
+        const OutT x = sweep_out<OutT, K>(a4[r], b4[r], key[r], pj, qj, thr);
+        if (x != x) continue;
+        mn = x < mn ? x : mn;
+        mx = x > mx ? x : mx;
+      }
+#pragma unroll
+      for (int m = kWave / 2; m > 0; m >>= 1) {
+        const OutT on = wave_xor(mn, m), ox = wave_xor(mx, m);
+        mn = on < mn ? on : mn;
+        mx = ox > mx ? ox : mx;
+      }
+      if (lane == 0) {
+        sm[wave][j][0] = fmin(sm[wave][j][0], (double)mn);
+        sm[wave][j][1] = fmax(sm[wave][j][1], (double)mx);
+      }
+    }
+  }
+  __syncthreads();
+  const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  for (int j = threadIdx.x; j < p.n_params; j += kThreads) {
+    double mn = sm[0][j][0], mx = sm[0][j][1];
+#pragma unroll
+    for (int w = 1; w < kThreads / kWave; ++w) {
+      mn = fmin(mn, sm[w][j][0]);
+      mx = fmax(mx, sm[w][j][1]);
+    }
+    p.part[(blk * p.n_params + j) * 2] = mn;
+    p.part[(blk * p.n_params + j) * 2 + 1] = mx;
+  }
+}
+
+// part[n][P][2] -> out[P][2]: workgroup j reduces parameter j over the n blocks
+__global__ __launch_bounds__(kThreads) void k_sweep_minmax2(const double* part, long long n, int n_params,
+                                                            double* out) {
+  __shared__ double smn[kThreads], smx[kThreads];
+  const int j = blockIdx.x;
+  double mn = INFINITY, mx = -INFINITY;
+  for (long long b = threadIdx.x; b < n; b += kThreads) {
+    mn = fmin(mn, part[(b * n_params + j) * 2]);
+    mx = fmax(mx, part[(b * n_params + j) * 2 + 1]);
+  }
+  smn[threadIdx.x] = mn;
+  smx[threadIdx.x] = mx;
+  __syncthreads();
+  for (int h = kThreads / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      smn[threadIdx.x] = fmin(smn[threadIdx.x], smn[threadIdx.x + h]);
+      smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + h]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[2 * j] = smn[0];
+    out[2 * j + 1] = smx[0];
+  }
+}
+
+// Predicted-count pass of parameters [j0, j0 + G): k_eval_pred's shape (one
+// thread per song column, a block of users per blockIdx.y, rows in flight),
+// each row's element combined G ways and compared against that parameter's
+// level floors; G x n_thr counters per thread, into pred[g][song][t].
+template <typename OutT, int K>
+__global__ __launch_bounds__(kThreads) void k_sweep_pred(SweepParams p, int j0) {
+  constexpr int G = kSweepG;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= p.width) return;
+  const int u0 = blockIdx.y * p.users_per_block, u1 = min(p.n_te, u0 + p.users_per_block);
+  const OutT* ubm = reinterpret_cast<const OutT*>(p.ubm);
+  const OutT* ibm = reinterpret_cast<const OutT*>(p.ibm);
+  const SweepTab* __restrict__ tab = p.tab;
+  const int ng = min(G, p.n_params - j0);
+  OutT xt[G][kThresholds];
+  double pg[G], qg[G];
+  long long tg[G];
+  int cnt[G][kThresholds];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int j = j0 + (g < ng ? g : 0);  // a short last group: the spare slots repeat its first, never stored
+    pg[g] = tab->p[j];
+    qg[g] = tab->q[j];
+    tg[g] = tab->thr[j];
+#pragma unroll
+    for (int t = 0; t < kThresholds; ++t) {
+      xt[g][t] = sizeof(OutT) == 4 ? (OutT)tab->xt_f[j][t] : (OutT)tab->xt_d[j][t];
+      cnt[g][t] = 0;
+    }
+  }
+  constexpr int U = MR_SWEEP_U;  // rows in flight per thread
+  const int s = p.song_lo + i;
+  const int s_blk = p.song_lo + blockIdx.x * kThreads;  // first song of the block
+  for (int ub = u0; ub < u1; ub += U) {
+    OutT a[U], b[U];
+    SweepKey<K> key[U] = {};
+#pragma unroll
+    for (int r = 0; r < U; ++r) {
+      a[r] = ub + r < u1 ? ubm[(size_t)(ub + r) * p.width + i] : (OutT)NAN;
+      b[r] = ub + r < u1 ? ibm[(size_t)(ub + r) * p.width + i] : (OutT)NAN;
+    }
+    if constexpr (K != MR_COMB_LINEAR) {
+#pragma unroll
+      for (int r = 0; r < U; ++r) {
+        key[r] = SweepKey<K>{};
+        if (ub + r >= u1) continue;
+        const long long t1 = p.te_off[ub + r + 1];
+        long long j = first_heard(p.te_songs, p.te_off[ub + r], t1, s_blk);  // uniform over the block
+        while (j < t1 && p.te_songs[j] < s) ++j;
+        const long long idx = sweep_pair(p, ub + r, s, j, t1);
+        if (idx < 0) a[r] = b[r] = (OutT)NAN;
+        key[r] = sweep_key<K>(p, idx);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < U; ++r)
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const OutT x = sweep_out<OutT, K>(a[r], b[r], key[r], pg[g], qg[g], tg[g]);
+#pragma unroll
+        for (int t = 0; t < kThresholds; ++t) cnt[g][t] += x >= xt[g][t] ? 1 : 0;  // NaN (no pair): never
+      }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {  // (conditions, not breaks: the counters stay in registers)
+    int* pred = p.pred + ((size_t)g * p.width + i) * p.n_thr;
+#pragma unroll
+    for (int t = 0; t < kThresholds; ++t) {
+      if (g < ng && t < p.n_thr) {
+        if (gridDim.y == 1) pred[t] = cnt[g][t];  // one user block: this thread owns the song's counts
+        else if (cnt[g][t]) atomicAdd(&pred[t], cnt[g][t]);
+      }
+    }
+  }
+}
+
+// True-positive pass of parameters [j0, j0 + ng): one thread per label (u, s),
+// as k_eval_tp, the element combined ng ways.
+template <typename OutT, int K>
+__global__ __launch_bounds__(kThreads) void k_sweep_tp(SweepParams p, int j0, int ng) {
+  const long long l = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (l >= p.n_lab) return;
+  const int u = p.lab_u[l], s = p.lab_s[l], i = s - p.song_lo;
+  if (i < 0 || i >= p.width) return;  // other shard, or a label-only song (never predicted)
+  OutT a = reinterpret_cast<const OutT*>(p.ubm)[(size_t)u * p.width + i];
+  OutT b = reinterpret_cast<const OutT*>(p.ibm)[(size_t)u * p.width + i];
+  SweepKey<K> key{};
+  if constexpr (K != MR_COMB_LINEAR) {
+    const long long t1 = p.te_off[u + 1];
+    const long long idx = sweep_pair(p, u, s, first_heard(p.te_songs, p.te_off[u], t1, s), t1);
+    if (idx < 0) return;
+    key = sweep_key<K>(p, idx);
+  }
+  const SweepTab* __restrict__ tab = p.tab;
+  for (int g = 0; g < ng; ++g) {
+    const int j = j0 + g;
+    const double x = (double)sweep_out<OutT, K>(a, b, key, tab->p[j], tab->q[j], tab->thr[j]);
+    if (x != x) continue;
+    const int c = levels(x, tab->mn[j], tab->mx[j], p.n_thr);
+    int* tp = p.tp + ((size_t)g * p.width + i) * p.n_thr;
+    for (int t = 0; t < c; ++t) atomicAdd(&tp[t], 1);
+  }
+}
+
+#define MR_SWEEP_LAUNCH(KERNEL, f64, kind, grid, st, ...)                                                        \
+  do {                                                                                                           \
+    if (f64) {                                                                                                   \
+      if (kind == MR_COMB_LINEAR)                                                                                \
+        hipLaunchKernelGGL((KERNEL<double, MR_COMB_LINEAR>), grid, dim3(kThreads), 0, st, __VA_ARGS__);          \
+      else if (kind == MR_COMB_AGGREGATION)                                                                      \
+        hipLaunchKernelGGL((KERNEL<double, MR_COMB_AGGREGATION>), grid, dim3(kThreads), 0, st, __VA_ARGS__);     \
+      else                                                                                                       \
+        hipLaunchKernelGGL((KERNEL<double, MR_COMB_STOCHASTIC>), grid, dim3(kThreads), 0, st, __VA_ARGS__);      \
+    } else {                                                                                                     \
+      if (kind == MR_COMB_LINEAR)                                                                                \
+        hipLaunchKernelGGL((KERNEL<float, MR_COMB_LINEAR>), grid, dim3(kThreads), 0, st, __VA_ARGS__);           \
+      else if (kind == MR_COMB_AGGREGATION)                                                                      \
+        hipLaunchKernelGGL((KERNEL<float, MR_COMB_AGGREGATION>), grid, dim3(kThreads), 0, st, __VA_ARGS__);      \
+      else                                                                                                       \
+        hipLaunchKernelGGL((KERNEL<float, MR_COMB_STOCHASTIC>), grid, dim3(kThreads), 0, st, __VA_ARGS__);       \
+    }                                                                                                            \
+    MR_HIP(hipGetLastError());                                                                                   \
+  } while (0)
+
+// One sweep call's state: the validated arguments, the context view and the
+// parameter table (host copy and its device twin).
+struct Sweep {
+  mr_view v;
+  int kind = 0, n_params = 0;
+  bool f64 = false;
+  hipStream_t st = nullptr;
+  SweepParams sp{};
+  SweepTab tab{};
+  Tmp<SweepTab> d_tab;
+
+  // validation in mr_combine_device's order; fills the table's p / q / thr
+  int open(mr_ctx* ctx, int kind_, int32_t n_params_, const double* params, uint64_t seed, int64_t pair_base,
+           int64_t n_pairs, const void* ubm, const void* ibm) {
+    if (!ctx || !params || !ubm || !ibm) return fail(MR_E_INVALID, "null argument");
+    if (kind_ != MR_COMB_LINEAR && kind_ != MR_COMB_AGGREGATION && kind_ != MR_COMB_STOCHASTIC)
+      return fail(MR_E_INVALID, "unknown combination kind %d", kind_);
+    if (n_params_ < 1 || n_params_ > kSweepMax)
+      return fail(MR_E_INVALID, "%d sweep parameters: 1 to %d", (int)n_params_, kSweepMax);
+    for (int j = 0; j < n_params_; ++j)  // MR:366-369 / MR:434-437
+      if (kind_ != MR_COMB_LINEAR && !(params[j] >= 0.0 && params[j] <= 1.0))
+        return fail(MR_E_INVALID, "percentage/probability %g (parameter %d) must be between 0 and 1", params[j], j);
+    int rc = mr_view_get(ctx, &v);
+    if (rc) return rc;
+    if (pair_base < 0 || n_pairs < 0) return fail(MR_E_INVALID, "negative pair_base / n_pairs");
+    MR_HIP(hipSetDevice(v.device));
+    kind = kind_;
+    n_params = n_params_;
+    f64 = v.out_dtype == MR_OUT_F64;
+    st = (hipStream_t)v.stream;
+    for (int j = 0; j < n_params; ++j) {
+      tab.p[j] = params[j];
+      tab.q[j] = 1.0 - params[j];
+      tab.thr[j] = (long long)(params[j] * (double)n_pairs);  // (p * length).toInt, MR:371
+      tab.mn[j] = INFINITY;
+      tab.mx[j] = -INFINITY;
+    }
+    sp.n_te = v.n_test_users;
+    sp.width = v.song_hi - v.song_lo;
+    sp.song_lo = v.song_lo;
+    sp.n_songs = v.n_songs;
+    sp.n_params = n_params;
+    sp.seed = (unsigned long long)seed;
+    sp.pair_base = (long long)pair_base;
+    sp.te_off = reinterpret_cast<const long long*>(v.te_off);
+    sp.te_songs = v.te_songs;
+    sp.ubm = ubm;
+    sp.ibm = ibm;
+    d_tab.st = st;
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_tab.p), sizeof(SweepTab), st));
+    sp.tab = d_tab.p;
+    return MR_OK;
+  }
+
+  int upload() {  // the host table is read when the copy is queued or before the call's last wait
+    MR_HIP(hipMemcpyAsync(d_tab.p, &tab, sizeof(SweepTab), hipMemcpyHostToDevice, st));
+    return MR_OK;
+  }
+
+  // extremes of every out_j over the shard's pairs (+inf / -inf without one); waits
+  int minmax(double* mn, double* mx) {
+    for (int j = 0; j < n_params; ++j) { mn[j] = INFINITY; mx[j] = -INFINITY; }
+    if (sp.width <= 0 || sp.n_te <= 0) return MR_OK;
+    int rc = upload();
+    if (rc) return rc;
+    const int gx = (sp.width + kThreads * kCombPer - 1) / (kThreads * kCombPer);
+    const int gy = std::max(1, std::min(sp.n_te, (8192 + gx - 1) / gx));
+    const long long nblk = (long long)gx * gy;
+    Tmp<double> part, out;
+    part.st = out.st = st;
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part.p), (size_t)nblk * n_params * 2 * sizeof(double), st));
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&out.p), (size_t)n_params * 2 * sizeof(double), st));
+    SweepParams q = sp;
+    q.part = part.p;
+    MR_SWEEP_LAUNCH(k_sweep_minmax, f64, kind, dim3(gx, gy), st, q);
+    hipLaunchKernelGGL(k_sweep_minmax2, dim3(n_params), dim3(kThreads), 0, st, part.p, nblk, n_params, out.p);
+    MR_HIP(hipGetLastError());
+    double h[kSweepMax * 2];
+    MR_HIP(hipMemcpyAsync(h, out.p, (size_t)n_params * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    MR_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < n_params; ++j) { mn[j] = h[2 * j]; mx[j] = h[2 * j + 1]; }
+    return MR_OK;
+  }
+
+  // The label classes' counts of every parameter into counts[P][2][n_classes]
+  // [n_thr] (device), groups of G parameters through one [G][width][n_thr]
+  // scratch pair: each group is gathered into the class block before the next
+  // reuses the scratch (stream order). mn / mx: the GLOBAL extremes. Waits.
+  int class_counts(const double* mn, const double* mx, const int64_t* lab_off, const int32_t* lab_songs,
+                   int32_t n_classes, const int32_t* classes, int32_t* counts, int n_thr) {
+    for (int j = 0; j < n_params; ++j) {
+      tab.mn[j] = mn[j];
+      tab.mx[j] = mx[j];
+      for (int t = 0; t < kThresholds; ++t) {
+        const bool on = t < n_thr && mn[j] <= mx[j];  // no pair: nothing passes (NaN floor)
+        tab.xt_f[j][t] = t >= n_thr ? INFINITY : on ? level_floor<float, uint32_t>(mn[j], mx[j], kThrHost[t]) : NAN;
+        tab.xt_d[j][t] = t >= n_thr ? INFINITY : on ? level_floor<double, uint64_t>(mn[j], mx[j], kThrHost[t]) : NAN;
+      }
+    }
+    const int width = sp.width, n_te = sp.n_te;
+    std::vector<int32_t> lu, ls;
+    int rc = label_pairs(n_te, lab_off, lab_songs, lu, ls);
+    if (rc) return rc;
+    const long long n_lab = lab_off[n_te];
+    if ((rc = upload())) return rc;
+    const size_t blk = (size_t)2 * n_classes * n_thr;  // one parameter's block
+    if (width <= 0 || n_te <= 0) {  // no element: every count is 0
+      if (blk) MR_HIP(hipMemsetAsync(counts, 0, blk * n_params * 4, st));
+      MR_HIP(hipStreamSynchronize(st));
+      return MR_OK;
+    }
+    Tmp<int> d_pred, d_tp, d_lu, d_ls, d_cls;
+    d_pred.st = d_tp.st = d_lu.st = d_ls.st = d_cls.st = st;
+    const size_t nc = (size_t)kSweepG * width * n_thr;
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_pred.p), nc * 4, st));
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_tp.p), nc * 4, st));
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_lu.p), lu.size() * 4, st));
+    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ls.p), ls.size() * 4, st));
+    MR_HIP(hipMemcpyAsync(d_lu.p, lu.data(), lu.size() * 4, hipMemcpyHostToDevice, st));
+    MR_HIP(hipMemcpyAsync(d_ls.p, ls.data(), ls.size() * 4, hipMemcpyHostToDevice, st));
+    if (n_classes > 0) {
+      MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cls.p), (size_t)n_classes * 4, st));
+      MR_HIP(hipMemcpyAsync(d_cls.p, classes, (size_t)n_classes * 4, hipMemcpyHostToDevice, st));
+    }
+    // the workgroup shape of eval_counts: users split only when the songs alone give too few workgroups
+    const int sx = (width + kThreads - 1) / kThreads;
+    const int uy = std::max(1, std::min((n_te + 15) / 16, (1024 + sx - 1) / sx));
+    SweepParams q = sp;
+    q.n_thr = n_thr;
+    q.users_per_block = (n_te + uy - 1) / uy;
+    q.pred = d_pred.p;
+    q.tp = d_tp.p;
+    q.lab_u = d_lu.p;
+    q.lab_s = d_ls.p;
+    q.n_lab = n_lab;
+    for (int j0 = 0; j0 < n_params; j0 += kSweepG) {
+      const int ng = std::min(kSweepG, n_params - j0);
+      if (uy > 1) MR_HIP(hipMemsetAsync(d_pred.p, 0, nc * 4, st));
+      MR_HIP(hipMemsetAsync(d_tp.p, 0, nc * 4, st));
+      MR_SWEEP_LAUNCH(k_sweep_pred, f64, kind, dim3(sx, uy), st, q, j0);
+      if (n_lab > 0) {
+        const int lb = (int)((n_lab + kThreads - 1) / kThreads);
+        MR_SWEEP_LAUNCH(k_sweep_tp, f64, kind, dim3(lb), st, q, j0, ng);
+      }
+      for (int g = 0; g < ng && n_classes > 0; ++g) {
+        const int n = n_classes * n_thr;
+        hipLaunchKernelGGL(k_eval_gather, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, st, n_classes, n_thr,
+                           v.song_lo, width, d_cls.p, d_pred.p + (size_t)g * width * n_thr,
+                           d_tp.p + (size_t)g * width * n_thr, counts + (size_t)(j0 + g) * blk);
+        MR_HIP(hipGetLastError());
+      }
+    }
+    MR_HIP(hipStreamSynchronize(st));  // the host staging (table, labels, classes) has been read
+    return MR_OK;
+  }
+};
+
+int sweep_thresholds(int32_t n_thresholds, int* n_thr) {
+  *n_thr = thresholds_or_default(n_thresholds);
+  if (*n_thr != 10 && *n_thr != 11)
+    return fail(MR_E_INVALID, "%d thresholds: 10 (MR:590) or 11 (distributed.scala:395)", *n_thr);
   return MR_OK;
 }
 
@@ -768,6 +1265,66 @@ int mr_eval_map_counts_device(mr_ctx* ctx, int32_t n_models, int32_t n_classes, 
     maps_out[m] = n_label_songs > 0 ? total / (double)n_label_songs : NAN;
   }
   return MR_OK;
+}
+
+int mr_sweep_minmax_device(mr_ctx* ctx, int kind, int32_t n_params, const double* params, uint64_t seed,
+                           int64_t pair_base, int64_t n_pairs, const void* ubm, const void* ibm, double* mn,
+                           double* mx) {
+  if (!mn || !mx) return fail(MR_E_INVALID, "null argument");
+  Sweep s;
+  int rc = s.open(ctx, kind, n_params, params, seed, pair_base, n_pairs, ubm, ibm);
+  if (rc) return rc;
+  return s.minmax(mn, mx);
+}
+
+int mr_sweep_class_counts_device(mr_ctx* ctx, int kind, int32_t n_params, const double* params, uint64_t seed,
+                                 int64_t pair_base, int64_t n_pairs, const void* ubm, const void* ibm,
+                                 const double* mn, const double* mx, const int64_t* lab_off,
+                                 const int32_t* lab_songs, int32_t n_classes, const int32_t* classes,
+                                 int32_t* counts, int32_t n_thresholds) {
+  if (!mn || !mx || !lab_off || !counts || (n_classes > 0 && !classes) || n_classes < 0)
+    return fail(MR_E_INVALID, "null argument");
+  for (int32_t c = 1; c < n_classes; ++c)
+    if (classes[c] <= classes[c - 1]) return fail(MR_E_INVALID, "classes not strictly ascending at %d", (int)c);
+  int n_thr;
+  int rc = sweep_thresholds(n_thresholds, &n_thr);
+  if (rc) return rc;
+  Sweep s;
+  if ((rc = s.open(ctx, kind, n_params, params, seed, pair_base, n_pairs, ubm, ibm))) return rc;
+  return s.class_counts(mn, mx, lab_off, lab_songs, n_classes, classes, counts, n_thr);
+}
+
+int mr_sweep_map_device(mr_ctx* ctx, int kind, int32_t n_params, const double* params, uint64_t seed,
+                        int64_t pair_base, int64_t n_pairs, const void* ubm, const void* ibm, const int64_t* lab_off,
+                        const int32_t* lab_songs, const int32_t* pos, int32_t n_label_songs, double* maps_out,
+                        double* minmax_out, int32_t n_thresholds) {
+  if (!lab_off || !pos || !maps_out) return fail(MR_E_INVALID, "null argument");
+  int n_thr;
+  int rc = sweep_thresholds(n_thresholds, &n_thr);
+  if (rc) return rc;
+  Sweep s;
+  if ((rc = s.open(ctx, kind, n_params, params, seed, pair_base, n_pairs, ubm, ibm))) return rc;
+  double mn[kSweepMax], mx[kSweepMax];
+  if ((rc = s.minmax(mn, mx))) return rc;
+  for (int j = 0; minmax_out && j < n_params; ++j) {
+    minmax_out[2 * j] = mn[j];
+    minmax_out[2 * j + 1] = mx[j];
+  }
+  for (int j = 0; j < n_params; ++j) {
+    if (!(mn[j] <= mx[j]))  // the reference throws here (MR:524)
+      return fail(MR_E_INVALID, "parameter %d (%g): the model has no pairs, min/max undefined", j, params[j]);
+  }
+  // the label classes (pos > 0, ascending) of the context's songs, as mr_eval_map_device
+  std::vector<int32_t> cls, cpos;
+  for (int g = s.v.song_lo; g < s.v.song_hi; ++g)
+    if (pos[g] > 0) { cls.push_back(g); cpos.push_back(pos[g]); }
+  const int nc = (int)cls.size();
+  Tmp<int> d_counts;
+  d_counts.st = s.st;
+  const size_t n = std::max<size_t>(1, (size_t)n_params * 2 * nc * n_thr);
+  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_counts.p), n * 4, s.st));
+  if ((rc = s.class_counts(mn, mx, lab_off, lab_songs, nc, cls.data(), d_counts.p, n_thr))) return rc;
+  return mr_eval_map_counts_device(ctx, n_params, nc, cpos.data(), d_counts.p, n_label_songs, maps_out, n_thr);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@ MN:8-123, src/main/scala/distributed.scala DS:55-602) on the MI355X engine.
 
     python -m musicrecommendation_amd.driver TRAIN_N TEST_N [--resources DIR]
         [--devices 0,1,...] [--song-shards G_s] [--user-blocks G_u] [--distributed] [--quiet]
+        [--sweep KIND:LO:HI:N ...]
 
 Same flow and output as main.scala: load train_{N}_{M}.txt, test_{N}_{M}.txt,
 test_labels_{N}_{M}.txt (MN:21-23), build the recommender (untimed, MN:27),
@@ -22,6 +23,13 @@ distributed.scala strategies 1/2 as a single call: song shards x user blocks,
 in-library RCCL across GPUs) and checked bit for bit against the
 single-context models. The reference's sequential/parallel pairs collapse into
 one GPU run each (seq = par holds by construction, README.md:254-261).
+
+--sweep KIND:LO:HI:N (repeatable; KIND = linear, aggregation or stochastic)
+runs after that flow: the mAP of that combination at N evenly spaced parameter
+values from LO to HI over the same two device models, one line per value and
+the best one — the experiment the reference's README leaves open, where the
+driver and main.scala hard-code 0.5 (DeviceEnsemble.sweep: no combined model
+is materialised).
 """
 from __future__ import annotations
 
@@ -29,7 +37,7 @@ import argparse
 import os
 import sys
 import time
-from typing import Callable, Optional, Sequence, TypeVar
+from typing import Callable, List, Optional, Sequence, Tuple, TypeVar
 
 T = TypeVar("T")
 
@@ -56,14 +64,40 @@ def round_at(p: int, x: float) -> float:
     return math.floor(x * s + 0.5) / s
 
 
+def parse_sweep(spec: str) -> Tuple[str, float, float, int]:
+    """--sweep KIND:LO:HI:N -> (kind, lo, hi, n); ValueError on a bad spec."""
+    from .ensemble import KINDS
+
+    parts = spec.split(":")
+    if len(parts) != 4:
+        raise ValueError(f"--sweep {spec!r}: expected KIND:LO:HI:N")
+    kind = parts[0]
+    if kind not in KINDS:
+        raise ValueError(f"--sweep {spec!r}: KIND must be one of {', '.join(KINDS)}")
+    try:
+        lo, hi, n = float(parts[1]), float(parts[2]), int(parts[3])
+    except ValueError:
+        raise ValueError(f"--sweep {spec!r}: LO and HI are numbers, N an integer") from None
+    if n < 1:
+        raise ValueError(f"--sweep {spec!r}: N must be at least 1")
+    return kind, lo, hi, n
+
+
+def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
+    """N evenly spaced values LO + i*(HI-LO)/(N-1) (N = 1: LO alone)."""
+    return [lo + i * (hi - lo) / (n - 1) for i in range(n)] if n > 1 else [lo]
+
+
 def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[int]] = None,
         song_shards: Optional[int] = None, user_blocks: int = 1, verbose: bool = True, seed: int = 1,
-        distributed: bool = False) -> dict:
+        distributed: bool = False, sweeps: Optional[Sequence[str]] = None) -> dict:
     import numpy as np
 
     from .dataset import Dataset
     from .engine import Engine
-    from .ensemble import DeviceEnsemble
+    from .ensemble import DeviceEnsemble, best
+
+    specs = [parse_sweep(s) if isinstance(s, str) else tuple(s) for s in (sweeps or [])]  # before any work
 
     n_thr = 11 if distributed else 10  # DS:395 vs MR:590
     if song_shards is None:  # one song shard per listed GPU and user block (DS:477-479's song partition)
@@ -109,9 +143,29 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
         maps[name] = timed(lambda: ens.threshold_map(t, n_thresholds=n_thr), f"{name} model mAP", verbose)  # MN:101-110
     for name, v in maps.items():
         print(f"{name} model mAP: {round_at(10, v)}", flush=True)                              # MN:112-121
+    swept = []
+    for kind, lo, hi, n in specs:
+        params = sweep_grid(lo, hi, n)
+        vals = timed(lambda: ens.sweep(kind, ubm, ibm, params, seed=seed, n_thresholds=n_thr),
+                     f"{kind} sweep ({n} values)", verbose)
+        for p, v in zip(params, vals):
+            print(f"{kind} sweep {p} mAP: {round_at(10, v)}", flush=True)
+        b = best(params, vals)
+        print(f"{kind} sweep best: {b} mAP: {round_at(10, vals[params.index(b)])}", flush=True)
+        swept.append({"kind": kind, "params": params, "mAP": vals, "best": b})
     eng.close()
-    return {"mAP": maps, "multi_gpu_checked": group_checked, "thresholds": n_thr,
-            "layout": (song_shards, user_blocks)}
+    out = {"mAP": maps, "multi_gpu_checked": group_checked, "thresholds": n_thr,
+           "layout": (song_shards, user_blocks)}
+    if specs:
+        out["sweeps"] = swept
+    return out
+
+
+def _sweep_arg(spec: str) -> Tuple[str, float, float, int]:
+    try:
+        return parse_sweep(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -127,11 +181,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--distributed", action="store_true",
                     help="distributed.scala's flow: defaults 300/10, 11-threshold mAP (DS:61-62, DS:395)")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--sweep", action="append", default=[], metavar="KIND:LO:HI:N", type=_sweep_arg,
+                    help="after the flow, the mAP of KIND (linear, aggregation, stochastic) at N evenly spaced "
+                         "parameter values from LO to HI; repeatable")
     a = ap.parse_args(argv)
     devices = [int(x) for x in a.devices.split(",") if x.strip()] if a.devices else None
     train_n = a.train_n if a.train_n is not None else (300 if a.distributed else 100)
     run(train_n, a.test_n, a.resources, devices, a.song_shards, a.user_blocks, verbose=not a.quiet, seed=a.seed,
-        distributed=a.distributed)
+        distributed=a.distributed, sweeps=a.sweep)
     return 0
 
 

@@ -320,6 +320,66 @@ class Engine:
             "mr_eval_map_counts_device")
         return out.tolist()
 
+    # ---- parameter sweep (mr_sweep_*: no combined model is materialised) ------
+    def _sweep_args(self, kind: int, params, seed: int, pair_base: int, n_pairs: int, ubm_ptr: int, ibm_ptr: int):
+        par = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+        return par, (self._h, int(kind), int(par.shape[0]), par.ctypes.data_as(ctypes.c_void_p),
+                     int(seed) & (2 ** 64 - 1), int(pair_base), int(n_pairs), ctypes.c_void_p(ubm_ptr),
+                     ctypes.c_void_p(ibm_ptr))
+
+    def sweep_minmax(self, kind: int, params, ubm_ptr: int, ibm_ptr: int, *, seed: int = 0, pair_base: int = 0,
+                     n_pairs: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(mins, maxs) over this context's pairs of the combination `kind` at
+        each parameter (mr_sweep_minmax_device; +inf / -inf without a pair)."""
+        par, args = self._sweep_args(kind, params, seed, pair_base, n_pairs, ubm_ptr, ibm_ptr)
+        mn = np.empty(max(1, par.shape[0]), dtype=np.float64)
+        mx = np.empty_like(mn)
+        _lib.check(self._L.mr_sweep_minmax_device(*args, mn.ctypes.data_as(ctypes.c_void_p),
+                                                  mx.ctypes.data_as(ctypes.c_void_p)), "mr_sweep_minmax_device")
+        return mn[:par.shape[0]], mx[:par.shape[0]]
+
+    def sweep_class_counts(self, kind: int, params, ubm_ptr: int, ibm_ptr: int, mins, maxs, lab_off: np.ndarray,
+                           lab_songs: np.ndarray, classes: np.ndarray, counts_ptr: int, *, seed: int = 0,
+                           pair_base: int = 0, n_pairs: int = 0, n_thresholds: int = 10) -> None:
+        """eval_class_counts with one "model" per parameter: the label classes'
+        (pred, tp) counts of every parameter into one device buffer of
+        len(params) x 2 x len(classes) x n_thresholds int32
+        (mr_sweep_class_counts_device; mins / maxs: the global extremes)."""
+        par, args = self._sweep_args(kind, params, seed, pair_base, n_pairs, ubm_ptr, ibm_ptr)
+        mn = np.ascontiguousarray(mins, dtype=np.float64)
+        mx = np.ascontiguousarray(maxs, dtype=np.float64)
+        if mn.shape != par.shape or mx.shape != par.shape:
+            raise ValueError("mins / maxs: one value per parameter")
+        lab_off = np.ascontiguousarray(lab_off, dtype=np.int64)
+        lab_songs = np.ascontiguousarray(lab_songs, dtype=np.int32)
+        classes = np.ascontiguousarray(classes, dtype=np.int32)
+        _lib.check(self._L.mr_sweep_class_counts_device(
+            *args, mn.ctypes.data_as(ctypes.c_void_p), mx.ctypes.data_as(ctypes.c_void_p),
+            lab_off.ctypes.data_as(ctypes.c_void_p), lab_songs.ctypes.data_as(ctypes.c_void_p), int(classes.shape[0]),
+            classes.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(counts_ptr), int(n_thresholds)),
+            "mr_sweep_class_counts_device")
+
+    def sweep_map(self, kind: int, params, ubm_ptr: int, ibm_ptr: int, lab_off: np.ndarray, lab_songs: np.ndarray,
+                  pos: np.ndarray, n_label_songs: int, *, seed: int = 0, pair_base: int = 0, n_pairs: int = 0,
+                  n_thresholds: int = 10, minmax: bool = False):
+        """Threshold mAP of the combination `kind` at each parameter, for a
+        context that holds the whole model (mr_sweep_map_device); with minmax
+        also each parameter's (min, max) as a len(params) x 2 array."""
+        par, args = self._sweep_args(kind, params, seed, pair_base, n_pairs, ubm_ptr, ibm_ptr)
+        lab_off = np.ascontiguousarray(lab_off, dtype=np.int64)
+        lab_songs = np.ascontiguousarray(lab_songs, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        if pos.shape[0] < self.song_hi:
+            raise ValueError("pos must cover the shard's songs")
+        out = np.empty(max(1, par.shape[0]), dtype=np.float64)
+        mm = np.empty((max(1, par.shape[0]), 2), dtype=np.float64)
+        _lib.check(self._L.mr_sweep_map_device(
+            *args, lab_off.ctypes.data_as(ctypes.c_void_p), lab_songs.ctypes.data_as(ctypes.c_void_p),
+            pos.ctypes.data_as(ctypes.c_void_p), int(n_label_songs), out.ctypes.data_as(ctypes.c_void_p),
+            mm.ctypes.data_as(ctypes.c_void_p) if minmax else None, int(n_thresholds)), "mr_sweep_map_device")
+        maps = out[:par.shape[0]].tolist()
+        return (maps, mm[:par.shape[0]]) if minmax else maps
+
     def timing_begin(self) -> None:
         """Open a timing window (one event on the engine stream)."""
         _lib.check(self._L.mr_timing_begin(self._h), "mr_timing_begin")

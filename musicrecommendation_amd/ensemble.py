@@ -15,6 +15,11 @@ models at once with one MAX all-reduce of their (-min, max) and one SUM
 all-reduce of a class-indexed count block built and folded on the device
 (mr_eval_class_counts_device / mr_eval_map_counts_device). Either way every
 rank computes the same mAP, bit for bit, for any layout.
+
+sweep answers what the combinations exist for — which parameter value to use
+(the reference hard-codes 0.5): the mAP of one combination kind at P values,
+the combination formed in registers (mr_sweep_*), no combined model written;
+across ranks the same two all-reduces as threshold_maps.
 """
 from __future__ import annotations
 
@@ -53,6 +58,32 @@ def eval_map(pred: np.ndarray, tp: np.ndarray, pos: np.ndarray, n_label_songs: i
                                       tp.ctypes.data_as(ctypes.c_void_p), pos.ctypes.data_as(ctypes.c_void_p),
                                       int(n_label_songs), ctypes.byref(out), int(pred.shape[1])), "mr_eval_map")
     return out.value
+
+
+KINDS = {"linear": LINEAR, "aggregation": AGGREGATION, "stochastic": STOCHASTIC}
+
+
+def sweep_kind(kind) -> int:
+    """A combination kind by name ("linear", "aggregation", "stochastic") or
+    MR_COMB_* code, as the code (unknown codes are the library's to reject)."""
+    if isinstance(kind, str):
+        if kind not in KINDS:
+            raise ValueError(f"unknown combination kind {kind!r}: one of {', '.join(KINDS)}")
+        return KINDS[kind]
+    return int(kind)
+
+
+def best(params, maps) -> float:
+    """The parameter of a sweep's highest mAP; the first one on ties (a NaN
+    mAP never wins)."""
+    params, maps = list(params), list(maps)
+    if not params or len(params) != len(maps):
+        raise ValueError("best: one mAP per parameter, at least one")
+    j = 0
+    for i in range(1, len(maps)):
+        if maps[i] > maps[j] or (maps[j] != maps[j] and maps[i] == maps[i]):
+            j = i
+    return params[j]
 
 
 class DeviceEnsemble:
@@ -282,6 +313,56 @@ class DeviceEnsemble:
         maps = self.e.eval_map_counts(len(names), counts.data_ptr(), cpos, self.n_label_songs,
                                       n_thresholds=n_thresholds)
         return dict(zip(names, maps))
+
+    # ---- parameter sweep -------------------------------------------------------
+    def sweep(self, kind, ubm, ibm, params, *, seed: int = 0, n_thresholds: int = 10) -> list:
+        """Threshold mAP (MR:636) of the combination `kind` ("linear" /
+        "aggregation" / "stochastic" or the MR_COMB_* code) at every value of
+        `params`, without materialising a combined model (mr_sweep_*): entry j
+        is bit-equal to threshold_map(linear / aggregation / stochastic(ubm,
+        ibm, params[j])). One context holding the whole model: one call. Several
+        ranks (or a song shard / user block): the route of threshold_maps — ONE
+        MAX all-reduce of every parameter's (-min, max), the class-count block
+        with one "model" per parameter, ONE SUM all-reduce of it (through the
+        host on gloo), the AP per class on the device."""
+        import torch
+        import torch.distributed as dist
+
+        kind = sweep_kind(kind)
+        params = [float(p) for p in params]
+        kw = dict(seed=seed, pair_base=self.pair_base, n_pairs=self.n_pairs)
+        reduce = self._reduce()
+        self._after_torch()
+        if not reduce and self.e.song_lo == 0 and self.e.song_hi == self.ds.n_songs:
+            return self.e.sweep_map(kind, params, ubm.data_ptr(), ibm.data_ptr(), self.ds.lab_off, self.ds.lab_songs,
+                                    self.pos, self.n_label_songs, n_thresholds=n_thresholds, **kw)
+        mins, maxs = self.e.sweep_minmax(kind, params, ubm.data_ptr(), ibm.data_ptr(), **kw)
+        if reduce:
+            be = dist.get_backend(self.group)
+            host = be != "nccl"
+            dev = torch.device("cpu") if host else self.device
+            mmt = torch.from_numpy(np.stack([-mins, maxs], axis=1).reshape(-1)).to(dev)
+            dist.all_reduce(mmt, op=dist.ReduceOp.MAX, group=self.group)
+            mmv = mmt.cpu().numpy().reshape(-1, 2)
+            mins, maxs = -mmv[:, 0], mmv[:, 1]
+        for p, mn, mx in zip(params, mins, maxs):
+            if not (mn <= mx):
+                raise ValueError(f"parameter {p}: model has no pairs: min/max undefined (the reference throws here, "
+                                 "MR:524)")
+        cls, cpos = self._classes()
+        cdev = self.device if torch.cuda.is_available() else torch.device("cpu")
+        counts = torch.empty((len(params), 2, cls.shape[0], n_thresholds), dtype=torch.int32, device=cdev)
+        self._after_torch()
+        self.e.sweep_class_counts(kind, params, ubm.data_ptr(), ibm.data_ptr(), mins, maxs, self.ds.lab_off,
+                                  self.ds.lab_songs, cls, counts.data_ptr(), n_thresholds=n_thresholds, **kw)
+        if reduce:
+            red = counts.cpu() if host and counts.is_cuda else counts
+            dist.all_reduce(red, op=dist.ReduceOp.SUM, group=self.group)
+            if red is not counts:
+                counts.copy_(red)
+            self._after_torch()  # the reduced block, written on torch's stream
+        return self.e.eval_map_counts(len(params), counts.data_ptr(), cpos, self.n_label_songs,
+                                      n_thresholds=n_thresholds)
 
     def topk(self, t) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Top-k recommendation lists of a dense device model (k = engine topk)."""

@@ -184,6 +184,19 @@ class MusicRecommender:
         torch.cuda.synchronize(ens.device)
         return ens.threshold_map(t)
 
+    def sweepCombinationModel(self, kind: str, params, seed: int = 0) -> List[Tuple[float, float]]:
+        """(param, mAP) of the combination `kind` ("linear", "aggregation",
+        "stochastic") at every value of `params` — the experiment the
+        reference's README leaves open (which alpha / percentage / probability
+        to use). Both models are computed on the device once and stay there;
+        no combined model and no host Model is built (DeviceEnsemble.sweep)."""
+        from .ensemble import DeviceEnsemble
+
+        params = [float(p) for p in params]
+        ens = DeviceEnsemble(self.engine())
+        ubm, ibm = ens.model("ubm"), ens.model("ibm")
+        return list(zip(params, ens.sweep(kind, ubm, ibm, params, seed=seed)))
+
     def _from_model(self, model: Model) -> np.ndarray:
         ds = self.dataset
         sidx = {ds.song_names(i): i for i in range(ds.n_songs)}
