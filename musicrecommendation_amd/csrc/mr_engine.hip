@@ -671,7 +671,7 @@ __device__ __forceinline__ void rank_survivors(int nc, int k, const long long* c
       for (int r = tid; r < k; r += NT) topk_dst_write(dst, r, out_k[r], out_s[r]);
     return;
   }
-  if (nc > 0) {  // candidate ranks: nc x nc comparisons, <= 16 per thread
+  if (nc > 0) {  // candidate ranks: nc x nc comparisons, about kRankQ<NT> per thread at most
     const int sl = NT / nc;  // slices per candidate (nc <= 256 <= NT)
     const int per = (nc + sl - 1) / sl;
     if (tid < sl * nc) {
@@ -3877,6 +3877,46 @@ using NbrKernel = void (*)(NbrParams);
 // Launch shapes (mr_options.stage1 / mr_launch_info).
 enum Shape { kShapeSeparate = 0, kShapeFused = 1, kShapeWide = 3 };
 
+// Everything mr_load decides about the ItemBasedModel's co-listening route
+// (plan_cooc), host side; the context keeps it beside the device buffers.
+// Default-constructed: the two-hop route, no rows.
+struct CoocPlan {
+  int route = 1;  // 1 two-hop, 2 co-listening index
+  // one row per distinct test-visible song with train listeners, heaviest first
+  std::vector<int32_t> row_song, te_row;  // the row's song; the row of every test entry (-1: none)
+  std::vector<int64_t> row_base;          // pool range starts (n_rows + 1)
+  std::vector<int64_t> row_reads;         // per row: c_tr(s2) + Σ_{v ∈ L_tr(s2)} |S(v) ∩ shard| (mr_cooc_bytes)
+  std::vector<int32_t> row_slots;         // light rows' hash slots | lanes per listener << kLightGlogShift
+  std::vector<int32_t> heavy_rows, light_rows;  // launch order: u32 rows, big u16 rows, the rest; light rows by tier
+  std::vector<int32_t> shard_deg;         // |S(v) ∩ [lo, hi)| of every (renumbered) train user
+  std::vector<int32_t> row_users;         // test users whose T(u) holds the row's song
+  std::vector<int32_t> row_listeners;     // per row: c_tr(s2)
+  std::vector<uint8_t> row_light;         // per row: built by the light-row kernels
+  int64_t build_reads = 0;                // Σ_r row_reads[r] (mr_cooc_stats)
+  int64_t pool_cap = 0;
+  int32_t max_shard_deg = 0;
+  int n_light_tier[6] = {0, 0, 0, 0, 0, 0};  // light rows per table tier (light_tier_slots), in launch order
+  bool all32 = false;              // every heavy row on the u32-counter kernel (is_u32_row)
+  int n_heavy32 = 0;               // the first heavy rows: u32 counters
+  int n_big16 = 0, tcap16 = 0, tcap32 = 0;  // big u16 rows after them; per-tile slot words
+  int dense_div = 0, force32 = 0;  // k_cooc_build's dense-segment rule
+  unsigned sat = 255;
+  // k_cooc_group (grp = 0: the per-tile k_cooc_build): tiles per group, groups,
+  // words per user record (load-time only) and per (row, listener) record
+  int grp = 0, n_grp = 0, urec_words = 0, lrec_words = 0;
+  int64_t n_lrec = 0;              // k_cooc_group's records: the u16 heavy rows' listeners
+  int64_t n_llrec = 0;             // k_cooc_light*'s records: the light rows' listeners
+  int group_nt = 1024;             // threads per k_cooc_group workgroup (MR_COOC_GNT)
+  int cooc_nt = 1024;              // threads of the co-listening scoring workgroups (MR_COOC_NT)
+  int n_rows() const { return (int)row_song.size(); }
+  int n_heavy() const { return (int)heavy_rows.size(); }  // rows built per (row, tile) or (row, tile group)
+  int n_light() const { return (int)light_rows.size(); }  // rows built per row (k_cooc_light)
+};
+
+// Heavy rows whose counts may pass 65535 (or every heavy row: MR_COOC_DENSE32,
+// MR_COOC_P16 = 0) take u32 counters and one listener walk per tile.
+inline bool is_u32_row(const CoocPlan& p, int32_t listeners) { return p.all32 || listeners >= 65536; }
+
 }  // namespace
 
 struct mr_ctx {
@@ -3937,31 +3977,17 @@ struct mr_ctx {
   DevBuf<unsigned> flag;           // mr_topk_dense_device: negative-score flag
   long long win_launches = 0;
   // co-listening route (mr_options.ibm_route, k_cooc_build)
-  int ibm_route = 1;               // 1 two-hop, 2 co-listening index
-  int cooc_nt = 1024;              // threads of the co-listening scoring workgroups (MR_COOC_NT)
-  size_t cooc_score_lds = 0;
-  int n_rows = 0, nseg = 0;
-  long long pool_cap = 0;
-  size_t cooc_lds = 0;
+  CoocPlan cooc;                   // the route and its host-side plan (cooc.route: 1 two-hop, 2 co-listening)
+  size_t cooc_score_lds = 0, cooc_lds = 0;
+  int nseg = 0;                    // row descriptors per scoring pass (setup_kernels)
   ScoreKernel cooc_kernel = nullptr;
   DevBuf<int> row_song, te_row, seg_len;
   DevBuf<long long> row_base, seg_off;
   DevBuf<unsigned> pool;
   DevBuf<unsigned> row_nnz;        // per run: each index row's non-zeros over the shard
-  std::vector<int32_t> row_users;  // test users whose T(u) holds the row's song
-  std::vector<int64_t> row_reads;  // per row: c_tr(s2) + Σ_{v ∈ L_tr(s2)} |S(v) ∩ shard| (mr_cooc_bytes)
-  std::vector<int32_t> row_listeners;  // per row: c_tr(s2)
-  std::vector<uint8_t> row_light;  // per row: built by the light-row kernels
-  long long build_reads = 0;       // Σ_r c_tr(s2) + Σ_{v ∈ L_tr(s2)} |S(v) ∩ shard| (mr_cooc_stats)
   bool cooc_ran = false;           // an ibm run on route 2 since the load (its row_nnz are current)
   hipStream_t side[2] = {nullptr, nullptr};  // light-row build streams (created with the context)
   hipEvent_t side_fork = nullptr, side_join[2] = {nullptr, nullptr};
-  int n_heavy = 0, n_light = 0;    // rows built per (row, tile) / per row (k_cooc_light)
-  int n_light_tier[6] = {0, 0, 0, 0, 0, 0};  // light rows per table tier (light_tier_slots), in launch order
-  int n_heavy32 = 0;               // the first heavy rows: >= 65536 listeners (u32 counters)
-  int n_big16 = 0, tcap16 = 0, tcap32 = 0;  // big u16 rows after them; per-tile slot words
-  int dense_div = 0, force32 = 0;  // k_cooc_build's dense-segment rule
-  unsigned sat = 255;
   size_t bstamp_off = 0;           // diagnostic build: k_cooc_build's stamps in the stamps buffer
   size_t lstamp_off = 0;           //   and the light rows' (one slot block per light row, launch order)
   DevBuf<int> rows_order, row_slots;  // heavy rows then light rows; light rows' hash slots
@@ -3971,8 +3997,6 @@ struct mr_ctx {
   DevBuf<unsigned> urec;           // k_cooc_group: per-user tile starts (load-time only: lrec's source)
   DevBuf<unsigned> lrec;           // k_cooc_group: per-(row, listener) base + tile-group starts
   DevBuf<uint2> llrec;             // k_cooc_light*: per-(row, listener) shard-row ranges
-  int grp = 0, n_grp = 0, urec_words = 0, lrec_words = 0;
-  int group_nt = 1024;             // threads per k_cooc_group workgroup (MR_COOC_GNT)
 
   void release_data() {
     tr_off.release(); te_off.release(); trs_off.release(); q_song.release();
@@ -3989,17 +4013,15 @@ struct mr_ctx {
     row_song.release(); te_row.release(); seg_len.release(); row_base.release(); seg_off.release();
     pool.release();
     rows_order.release(); row_slots.release(); sr_off.release(); sr_songs.release(); row_nnz.release();
-    urec.release(); lrec.release(); llrec.release(); rdesc.release(); grp = n_grp = urec_words = lrec_words = 0;
-    row_users.clear(); row_reads.clear(); row_listeners.clear(); row_light.clear();
-    build_reads = 0; cooc_ran = false;
-    ibm_route = 1; n_rows = 0; nseg = 0; pool_cap = 0; cooc_kernel = nullptr; n_heavy = n_light = n_heavy32 = 0;
-    for (int& x : n_light_tier) x = 0;
+    urec.release(); lrec.release(); llrec.release(); rdesc.release();
+    cooc = CoocPlan{};
+    cooc_kernel = nullptr;
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
     graph_exec = nullptr;
     graph = nullptr;
     graph_steps = 0;
-    loaded = ran = false;
+    loaded = ran = cooc_ran = false;
   }
 };
 
@@ -4230,13 +4252,13 @@ void pick_kernels(mr_ctx* c) {
       c->score_kernel[MODEL] = f64 ? k_score_wide<MODEL, double, kWideThreads, kMaxTopkLarge, false>
                                    : k_score_wide<MODEL, float, kWideThreads, kMaxTopkLarge, false>;
     if constexpr (MODEL == MR_IBM) {
-      if (c->ibm_route == 2 && c->cooc_nt == 512) {
+      if (c->cooc.route == 2 && c->cooc.cooc_nt == 512) {
         if (c->opt.topk == 10)
           c->cooc_kernel = f64 ? k_score_wide<MR_IBM, double, 512, 10, true> : k_score_wide<MR_IBM, float, 512, 10, true>;
         else
           c->cooc_kernel = f64 ? k_score_wide<MR_IBM, double, 512, kMaxTopkLarge, true>
                                : k_score_wide<MR_IBM, float, 512, kMaxTopkLarge, true>;
-      } else if (c->ibm_route == 2) {
+      } else if (c->cooc.route == 2) {
         if (c->opt.topk == 10)
           c->cooc_kernel = f64 ? k_score_wide<MR_IBM, double, kWideThreads, 10, true>
                                : k_score_wide<MR_IBM, float, kWideThreads, 10, true>;
@@ -4343,6 +4365,759 @@ static int check_dataset(const mr_dataset* d, std::vector<int32_t>& col_tr) {
   trace("validate");
   return MR_OK;
 }
+
+// ---- mr_load's stages: host plans (no HIP call), then uploads ----------------
+namespace {
+
+// The train side of a load: users renumbered (new id -> caller's id in perm),
+// their CSR, the song -> listeners transpose and the bulk passes' worker cuts.
+struct TrainIndex {
+  int W = 1;                  // workers of the bulk passes
+  std::vector<int64_t> ucut;  // their user ranges, about equal entries each
+  std::vector<int32_t> perm, len;
+  std::vector<int64_t> off, trs_off;
+  mr_par::buffer<int32_t> songs, trs_users;
+};
+
+// Train users renumbered by distinct-song count, descending (ties by id),
+// unless opt.train_order = 1: the users of one wave then have segments of
+// similar length in every song tile, so no lane waits on one heavy
+// listener's long tail (heavy listeners dominate every neighbourhood).
+// Results do not change: every accumulation is an order-free integer sum
+// and the outputs are indexed by test user and song only. (A stable
+// counting sort by degree.)
+void renumber_train(const mr_dataset* d, int train_order, TrainIndex& ti) {
+  const int n_tr = d->n_train_users;
+  ti.perm.resize(std::max(1, n_tr));
+  if (train_order == 0 && n_tr > 0) {
+    int64_t max_deg = 0;
+    for (int v = 0; v < n_tr; ++v) max_deg = std::max(max_deg, d->tr_off[v + 1] - d->tr_off[v]);
+    std::vector<int64_t> at((size_t)max_deg + 1, 0);
+    for (int v = 0; v < n_tr; ++v) at[max_deg - (d->tr_off[v + 1] - d->tr_off[v])]++;
+    int64_t run = 0;
+    for (auto& x : at) { const int64_t n = x; x = run; run += n; }
+    for (int v = 0; v < n_tr; ++v) ti.perm[at[max_deg - (d->tr_off[v + 1] - d->tr_off[v])]++] = v;
+  } else {
+    for (int v = 0; v < n_tr; ++v) ti.perm[v] = v;
+  }
+  ti.off.assign((size_t)n_tr + 1, 0);
+  mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
+    for (int64_t v = a; v < b; ++v) ti.off[v] = d->tr_off[ti.perm[v] + 1] - d->tr_off[ti.perm[v]];
+  });
+  ti.off[n_tr] = mr_par::exclusive_scan(ti.off.data(), (int64_t)n_tr);
+  ti.songs.resize((size_t)std::max<int64_t>(1, d->tr_off[n_tr]));
+  ti.len.resize(std::max(1, n_tr));
+  mr_par::parallel_dynamic(n_tr, 2048, [&](int64_t v, int) {
+    const int o = ti.perm[v];
+    std::copy(d->tr_songs + d->tr_off[o], d->tr_songs + d->tr_off[o + 1], ti.songs.begin() + ti.off[v]);
+    ti.len[v] = d->tr_len[o];
+  });
+}
+
+// Transpose song -> train users, lists ascending in v: worker w owns a
+// contiguous range of (new) users and a private cursor per song.
+void transpose_train(int n_tr, int n_s, TrainIndex& ti) {
+  const int W = ti.W;
+  ti.ucut = weighted_cuts(ti.off.data(), n_tr, W);
+  const std::vector<int64_t>&tr_off = ti.off, &trs_off = ti.trs_off, &ucut = ti.ucut;
+  const int32_t* tr_songs = ti.songs.data();
+  ti.trs_users.resize((size_t)std::max<int64_t>(1, trs_off[n_s]));
+  std::vector<std::vector<int64_t>> pos(W);
+  mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
+    for (int64_t w = w0; w < w1; ++w) {
+      pos[w].assign(n_s, 0);
+      for (int64_t i = tr_off[ucut[w]]; i < tr_off[ucut[w + 1]]; ++i) pos[w][tr_songs[i]]++;
+    }
+  }, 1, W);
+  mr_par::parallel_for(n_s, [&](int64_t a, int64_t b, int) {
+    for (int64_t s2 = a; s2 < b; ++s2) {
+      int64_t at = trs_off[s2];
+      for (int w = 0; w < W; ++w) {
+        const int64_t n = pos[w][s2];
+        pos[w][s2] = at;
+        at += n;
+      }
+    }
+  }, 4096);
+  mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
+    for (int64_t w = w0; w < w1; ++w)
+      for (int64_t v = ucut[w]; v < ucut[w + 1]; ++v)
+        for (int64_t i = tr_off[v]; i < tr_off[v + 1]; ++i) ti.trs_users[pos[w][tr_songs[i]]++] = (int32_t)v;
+  }, 1, W);
+}
+
+// Shard geometry, launch shape, tiling, stage-1 chunking and the two-hop
+// batch of one load, with every shape / LDS / limit check.
+struct LaunchPlan {
+  int lo = 0, hi = 0, width = 0, k = 0;
+  int shape = kShapeSeparate;
+  int chunk = 1, n_chunks = 1;  // stage 1 of the separate / wide shapes: one LDS chunk of train users per workgroup
+  int block_songs = 0, n_tiles = 0;
+  int cap = 0, batch = 0;
+  bool fused() const { return shape == kShapeFused; }
+  bool wide() const { return shape == kShapeWide; }
+};
+
+int plan_launch(const mr_options& opt, int n_tr, int n_te, int n_s, size_t free_b, int dev_share, LaunchPlan& p) {
+  const int lo = opt.song_lo, hi = opt.song_hi > 0 ? opt.song_hi : n_s;
+  if (lo < 0 || hi > n_s || lo >= hi) return fail(MR_E_INVALID, "song shard [%d,%d) invalid for %d songs", lo, hi, n_s);
+  const int width = hi - lo;
+  const int k = opt.topk;
+  p.lo = lo; p.hi = hi; p.width = width; p.k = k;
+  p.shape = pick_shape(opt, n_tr, n_te);
+  const bool fused = p.fused(), wide = p.wide();
+  if (wide && k > kMaxTopkLarge)
+    return fail(MR_E_INVALID, "wide shape keeps topk <= %d (got %d)", kMaxTopkLarge, k);
+  if (fused && n_tr > kMaxFusedTrainUsers)
+    return fail(MR_E_INVALID, "fused stage 1 needs n_train_users <= %d (got %d)", kMaxFusedTrainUsers, n_tr);
+  const int chunk = stage1_chunk_for(opt, n_tr);
+  if ((n_tr + chunk - 1) / chunk > kMaxChunks)
+    return fail(MR_E_INVALID, "stage1_chunk %d gives more than %d chunks", chunk, kMaxChunks);
+  const int n_chunks = (std::max(1, n_tr) + chunk - 1) / chunk;
+  int bs;
+  if (wide) {
+    // the widest tile the LDS holds (every tile re-walks the user's whole
+    // neighbour list), then balanced: n_tiles = ceil(width / max), bs =
+    // ceil(width / n_tiles) rounded up to 256
+    const int bmax = wide_bmax(k, n_chunks);
+    const long long nt = ((long long)width + bmax - 1) / bmax;
+    bs = opt.block_songs > 0 ? opt.block_songs
+                             : (int)std::min<long long>(bmax, (((long long)width + nt - 1) / nt + 255) / 256 * 256);
+    if (wide_lds<kWideThreads>(bs, k, n_chunks).total > kLdsBytes)
+      return fail(MR_E_INVALID, "wide shape: block_songs %d needs more than %d B of LDS", bs, kLdsBytes);
+  } else {
+    bs = opt.block_songs > 0 ? opt.block_songs : auto_block_songs(width, n_te, fused, k, n_tr);
+  }
+  if (fused && bs > 8192) return fail(MR_E_INVALID, "fused stage 1 needs block_songs <= 8192 (got %d)", bs);
+  if (!wide && k > kMaxTopkLarge && bs > kMaxTopkTile)
+    return fail(MR_E_INVALID, "with topk > %d block_songs must be <= %d (got %d)", kMaxTopkLarge, kMaxTopkTile, bs);
+  p.chunk = chunk; p.n_chunks = n_chunks;
+  p.block_songs = bs;
+  p.n_tiles = (width + bs - 1) / bs;
+  // Separate / wide shapes: test-user batches so the neighbour lists fit 8 GiB.
+  p.cap = n_chunks * chunk;
+  // one launch's neighbour lists (batch x cap x 12 B): an eighth of the free
+  // device memory, 8-32 GiB (C5's 2,000 users in one launch on a 288 GB
+  // MI355X; allocated at the first two-hop run, ensure_nbr)
+  const size_t budget = std::min<size_t>((size_t)32 << 30, std::max<size_t>((size_t)8 << 30, free_b / 8)) /
+                        (size_t)std::max(1, dev_share);
+  p.batch = fused ? n_te
+                  : (int)std::max<size_t>(1, std::min<size_t>(std::min(n_te, 65528), budget / ((size_t)p.cap * 12)));
+  return MR_OK;
+}
+
+// Per-song / per-user fixed-point tables, computed once on the host with
+// correctly rounded std::sqrt (java.lang.Math.sqrt semantics, MR:147/237).
+struct ScaleTables {
+  std::vector<double> sqrt_c, sqrt_tr, sqrt_te;
+  std::vector<long long> q_song;
+  std::vector<float> rsq_c;
+};
+
+ScaleTables make_scales(const mr_dataset* d, const TrainIndex& ti, int frac_bits) {
+  const int n_tr = d->n_train_users, n_te = d->n_test_users, n_s = d->n_songs;
+  const double two_f = std::ldexp(1.0, frac_bits);
+  ScaleTables t;
+  t.sqrt_c.resize(n_s); t.sqrt_tr.resize(std::max(1, n_tr)); t.sqrt_te.resize(n_te);
+  t.q_song.resize(n_s);
+  t.rsq_c.resize(n_s);
+  mr_par::parallel_for(n_s, [&](int64_t a, int64_t b, int) {
+    for (int64_t s2 = a; s2 < b; ++s2) {
+      t.sqrt_c[s2] = std::sqrt((double)d->song_count[s2]);
+      t.q_song[s2] = (long long)std::nearbyint(two_f / t.sqrt_c[s2]);
+      t.rsq_c[s2] = t.sqrt_c[s2] > 0.0 ? (float)(1.0 / t.sqrt_c[s2]) : 0.f;
+    }
+  });
+  mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
+    for (int64_t v = a; v < b; ++v) t.sqrt_tr[v] = std::sqrt((double)ti.len[v]);
+  });
+  for (int u = 0; u < n_te; ++u) t.sqrt_te[u] = std::sqrt((double)d->te_len[u]);
+  return t;
+}
+
+// Tile-major train CSR over the shard's songs: for tile t, user v, the
+// tile-local ids of S(v) ∩ [lo + t*bs, lo + (t+1)*bs) live at
+// tsongs[toff[t*n_tr + v] .. toff[t*n_tr + v + 1]) (entries ordered by
+// (tile, user, song)), so neighbouring users' segments share cache lines.
+struct TileCsr {
+  mr_par::buffer<int32_t> toff;
+  mr_par::buffer<uint16_t> tsongs;
+};
+
+// Every user writes only its own (tile, user) slots: parallel over users.
+void build_tiles(const TrainIndex& ti, const LaunchPlan& lp, int n_tr, TileCsr& out) {
+  const int lo = lp.lo, hi = lp.hi, bs = lp.block_songs, W = ti.W;
+  const int64_t* tr_off = ti.off.data();
+  const int32_t* tr_songs = ti.songs.data();
+  const std::vector<int64_t>& ucut = ti.ucut;
+  const size_t n_tv = (size_t)lp.n_tiles * n_tr;
+  mr_par::buffer<int32_t>& toff = out.toff;
+  toff.resize(n_tv + 1);
+  mr_par::parallel_for((int64_t)n_tv, [&](int64_t a, int64_t b, int) { std::fill(toff.begin() + a, toff.begin() + b, 0); });
+  mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
+    for (int64_t w = w0; w < w1; ++w)
+      for (int64_t v = ucut[w]; v < ucut[w + 1]; ++v)
+        for (int64_t i = tr_off[v]; i < tr_off[v + 1]; ++i) {
+          const int s2 = tr_songs[i];
+          if (s2 >= lo && s2 < hi) toff[(size_t)((s2 - lo) / bs) * n_tr + v]++;
+        }
+  }, 1, W);
+  const int64_t n_entries = mr_par::exclusive_scan(toff.data(), (int64_t)n_tv);
+  toff[n_tv] = (int32_t)n_entries;
+  // padded to whole 8-B words (+1): the wide kernel loads a segment's ids as
+  // aligned 4-id words
+  mr_par::buffer<uint16_t>& tsongs = out.tsongs;
+  tsongs.resize((std::max<int64_t>(1, n_entries) + 3) / 4 * 4 + 4);
+  std::fill(tsongs.begin() + n_entries, tsongs.end(), (uint16_t)0);
+  mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
+    for (int64_t w = w0; w < w1; ++w)
+      for (int64_t v = ucut[w]; v < ucut[w + 1]; ++v) {
+        int cur_t = -1;
+        int32_t at = 0;
+        for (int64_t i = tr_off[v]; i < tr_off[v + 1]; ++i) {  // songs ascend, so tiles do
+          const int s2 = tr_songs[i];
+          if (s2 < lo || s2 >= hi) continue;
+          const int t = (s2 - lo) / bs;
+          if (t != cur_t) {
+            cur_t = t;
+            at = toff[(size_t)t * n_tr + v];
+          }
+          tsongs[at++] = (uint16_t)(s2 - lo - t * bs);
+        }
+      }
+  }, 1, W);
+}
+
+// ---- the co-listening route's plan (CoocPlan) --------------------------------
+// What the planning steps share: the load's inputs, read only.
+struct CoocIn {
+  const mr_dataset* d;
+  const mr_options& opt;
+  const TrainIndex& ti;
+  const LaunchPlan& lp;
+  const std::vector<int32_t>& col_tr;  // distinct train listeners per song
+};
+
+// Lanes per listener of rows_walk, as a log2: the largest power of 2 G <= 16
+// with 6 G <= per, the entries one listener brings (>= 6 per lane).
+int walk_glog(int64_t per) {
+  int glog = 0;
+  while (glog < 4 && ((int64_t)6 << (glog + 1)) <= per) ++glog;
+  return glog;
+}
+
+// The index's rows: one per distinct test-visible song with train listeners,
+// heaviest first; te_row maps every test entry to its row. Returns why the
+// route cannot take these rows, or null.
+const char* cooc_rows(const CoocIn& in, CoocPlan& p) {
+  const mr_dataset* d = in.d;
+  const std::vector<int32_t>& col_tr = in.col_tr;
+  const int n_s = d->n_songs;
+  const int64_t nte = d->te_off[d->n_test_users];
+  int32_t max_c = 0;
+  std::vector<int32_t> row_of(n_s, -1);
+  for (int64_t i = 0; i < nte; ++i) {
+    const int s2 = d->te_songs[i];
+    if (col_tr[s2] > 0 && row_of[s2] < 0) { row_of[s2] = 0; p.row_song.push_back(s2); }
+  }
+  std::sort(p.row_song.begin(), p.row_song.end(), [&](int x, int y) {
+    return col_tr[x] != col_tr[y] ? col_tr[x] > col_tr[y] : x < y;
+  });
+  for (size_t r = 0; r < p.row_song.size(); ++r) {
+    row_of[p.row_song[r]] = (int32_t)r;
+    max_c = std::max(max_c, col_tr[p.row_song[r]]);
+  }
+  p.te_row.resize(std::max<int64_t>(1, nte));
+  for (int64_t i = 0; i < nte; ++i) p.te_row[i] = row_of[d->te_songs[i]];
+  if (max_c > (int32_t)kCoocCntMask) return "train listener counts < 131072";
+  // the row descriptors hold 32-bit listener-list starts and k_urec's
+  // records 32-bit shard-row bases (shard entries <= train entries)
+  if (in.ti.trs_off[n_s] >= (int64_t)INT32_MAX) return "train entries < 2^31";
+  if ((long long)p.row_song.size() * in.lp.n_tiles > INT32_MAX) return "rows x tiles < 2^31";
+  return nullptr;
+}
+
+// |S(v) ∩ [lo, hi)| of every (renumbered) train user, then the row bounds:
+// row r's pool range holds at most min(width, Σ_{v ∈ L_tr(s2)} |S(v) ∩ shard|)
+// entries (its non-zero counts over the shard's songs). Route auto: null
+// unless the cost model prefers the two-hop route.
+const char* cooc_bounds(const CoocIn& in, CoocPlan& p) {
+  const mr_dataset* d = in.d;
+  const TrainIndex& ti = in.ti;
+  const int n_tr = d->n_train_users, n_te = d->n_test_users, lo = in.lp.lo, hi = in.lp.hi;
+  std::vector<int32_t>& deg = p.shard_deg;
+  deg.resize((size_t)std::max(1, n_tr));
+  mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
+    for (int64_t v = a; v < b; ++v) {
+      const int32_t* r0 = ti.songs.data() + ti.off[v];
+      const int32_t* r1 = ti.songs.data() + ti.off[v + 1];
+      deg[v] = (int32_t)(std::lower_bound(r0, r1, hi) - std::lower_bound(r0, r1, lo));
+    }
+  });
+  for (int v = 0; v < n_tr; ++v) p.max_shard_deg = std::max(p.max_shard_deg, deg[v]);
+  const int64_t nr = p.n_rows();
+  p.row_base.assign((size_t)nr + 1, 0);
+  p.row_reads.assign((size_t)nr, 0);
+  mr_par::parallel_for(nr, [&](int64_t a, int64_t b, int) {
+    for (int64_t r = a; r < b; ++r) {
+      const int s2 = p.row_song[r];
+      int64_t sum = 0;
+      for (int64_t i = ti.trs_off[s2]; i < ti.trs_off[s2 + 1]; ++i) sum += deg[ti.trs_users[i]];
+      p.row_reads[r] = (ti.trs_off[s2 + 1] - ti.trs_off[s2]) + sum;
+      p.row_base[r] = std::min<int64_t>(sum, in.lp.width);  // the row's non-zeros: its sparse bound
+    }
+  }, 256);
+  // auto: the cost model of cooc_pays (the rows' bounds = sparse entry bounds here)
+  if (in.opt.ibm_route == 0) {
+    double e_est = 0.0;
+    for (int64_t i = 0; i < d->te_off[n_te]; ++i)
+      if (p.te_row[i] >= 0) e_est += (double)p.row_base[p.te_row[i]];
+    double v_est = 0.0;
+    for (int u = 0; u < n_te; ++u) {
+      double sc = 0.0;
+      for (int64_t i = d->te_off[u]; i < d->te_off[u + 1]; ++i) sc += in.col_tr[d->te_songs[i]];
+      v_est += std::min<double>(sc, n_tr);
+    }
+    if (!cooc_pays(v_est * in.lp.n_tiles, e_est, p.row_base, p.row_reads, p.row_song, in.col_tr, in.lp.n_tiles))
+      return "a cheaper estimate than the two-hop route (auto)";
+  }
+  return nullptr;
+}
+
+// Light rows (k_cooc_light: the bound fits half the hash slots) and heavy rows
+// (k_cooc_build / k_cooc_group), the heavy rows' order and slots, the tile
+// groups, and every row's pool range (row_base: bounds in, starts out).
+void cooc_split(const CoocIn& in, CoocPlan& p) {
+  const std::vector<int32_t>& col_tr = in.col_tr;
+  const int width = in.lp.width, n_tiles = in.lp.n_tiles, bs = in.lp.block_songs;
+  const int64_t nr = p.n_rows();
+  const bool light_ok = width <= kLightMaxWidth && n_tiles <= kLightMaxTiles && cooc_light_opt();
+  // a light row's table: the smallest power of 2 of at least bound * 100 / lload slots (the
+  // entry bound at most lload % of the slots), at most light_slots_max (MR_COOC_LIGHT_MAX /
+  // MR_COOC_LIGHT_LOAD: A/B knobs; defaults 32768 slots, 80 %)
+  // narrow shard: the group kernel would hold every tile in one pass
+  // (the conditions of its set-up below, before the heavy rows are known)
+  bool narrow = false;
+  if (cooc_group_opt() && 1 + (n_tiles + 2) / 2 <= 32 && p.max_shard_deg <= 65535 &&
+      n_tiles <= std::min(kMaxGroupTiles, cooc_group_max_opt()))
+    narrow = cooc_group_lds(bs, n_tiles) <= kLdsBytes;
+  const int64_t lload = cooc_light_load_opt(), light_slots_max = cooc_light_max_opt(narrow);
+  p.dense_div = cooc_dense_div_opt();
+  // a dense segment holds whole interleaved blocks (cooc_dense_words):
+  // the words past its songs' bytes, over every tile, on each heavy row's bound
+  int64_t dense_pad = 0;
+  for (int t = 0; t < n_tiles; ++t) {
+    const int bw = (int)(std::min<int64_t>(width, (int64_t)(t + 1) * bs) - (int64_t)t * bs);
+    dense_pad += cooc_dense_words(bw) - (bw + 3) / 4;
+  }
+  // whole 16-B words: every row's bound stays a multiple of 4 words, so
+  // every row (placed by the exclusive scan below) starts 16-B aligned for
+  // the scorer's dvec_t loads and k_cooc_group's chunk_t stores
+  dense_pad = (dense_pad + 3) & ~(int64_t)3;
+  p.row_slots.assign((size_t)std::max<int64_t>(1, nr), 0);
+  for (int64_t r = 0; r < nr; ++r) {
+    const int64_t c = col_tr[p.row_song[r]];
+    if (light_ok && p.row_base[r] * 100 <= light_slots_max * lload && c <= (int32_t)kLightCntMask) {
+      int sl = 1024;
+      while ((int64_t)sl * lload < p.row_base[r] * 100) sl <<= 1;
+      // lanes per listener: by the row's shard entries per listener
+      p.row_slots[r] = sl | (walk_glog(c > 0 ? (p.row_reads[r] - c) / c : 0) << kLightGlogShift);
+      p.light_rows.push_back((int32_t)r);
+      p.row_base[r] = (p.row_base[r] + 3) & ~(int64_t)3;
+    } else {
+      // k_cooc_build: a tile's segment is sparse (its non-zeros) or dense
+      // (<= kCoocDenseDiv x its non-zeros, <= the tile's songs), in whole
+      // 16-B words (32-B for u32 counts)
+      // (dense: count bytes <= kCoocDenseDiv / 4 x the non-zeros, + excess entries <= the non-zeros)
+      const int64_t nz = p.row_base[r];
+      const int64_t dn = std::max<int64_t>(1, std::min<int64_t>(p.dense_div, width)) * nz;
+      p.row_base[r] = ((std::min<int64_t>(width, dn) + nz + 3) & ~(int64_t)3) + 8 * (int64_t)n_tiles + dense_pad;
+      p.heavy_rows.push_back((int32_t)r);
+    }
+  }
+  std::vector<int32_t>& heavy_rows = p.heavy_rows;
+  // heavy rows whose counts may pass 65535 first (u32 counters), the rest
+  // keep their order (u16-pair counters, k_cooc_build<.., true>)
+  p.force32 = cooc_dense32_opt();
+  p.all32 = !MR_COOC_P16 || p.force32;
+  std::stable_partition(heavy_rows.begin(), heavy_rows.end(),
+                        [&](int32_t r) { return is_u32_row(p, col_tr[p.row_song[r]]); });
+  for (int32_t r : heavy_rows) p.n_heavy32 += is_u32_row(p, col_tr[p.row_song[r]]) ? 1 : 0;
+  // Big rows (>= kCoocBigRow listeners, and every u32 row): one workgroup
+  // per (row, tile), each tile a fixed slot of tcap words (the larger of a
+  // dense segment and the longest sparse one), so the row's tiles run in
+  // parallel. Rows are heaviest first, so the big rows of each kind lead.
+  const int sparse_max = p.dense_div > 0 ? (bs + p.dense_div - 1) / p.dense_div : bs;
+  // a dense segment: the count bytes + at most one excess entry per song
+  p.tcap32 = (std::max(sparse_max, cooc_dense_words(bs) + bs) + 7) & ~7;
+  p.tcap16 = p.tcap32;
+  for (size_t i = p.n_heavy32; i < heavy_rows.size(); ++i) {
+    if (col_tr[p.row_song[heavy_rows[i]]] < kCoocBigRow) break;
+    p.n_big16++;
+  }
+  for (size_t i = 0; i < heavy_rows.size(); ++i)
+    if ((int)i < p.n_heavy32 + p.n_big16)
+      p.row_base[heavy_rows[i]] = (int64_t)n_tiles * ((int)i < p.n_heavy32 ? p.tcap32 : p.tcap16);
+  // The u16 heavy rows by tile groups (k_cooc_group) when the per-user
+  // records fit (one 128-B line: n_tiles <= 61, u16 starts: shard rows
+  // < 65536 songs): the widest group whose counters fit the LDS.
+  p.group_nt = cooc_group_nt_opt();
+  p.urec_words = 1 + (n_tiles + 2) / 2;
+  if (cooc_group_opt() && p.n_heavy() > p.n_heavy32 && p.urec_words <= 32 && p.max_shard_deg <= 65535) {
+    p.grp = std::min(std::min(n_tiles, kMaxGroupTiles), cooc_group_max_opt());
+    while (p.grp > 0 && cooc_group_lds(bs, p.grp) > kLdsBytes) --p.grp;
+  }
+  if (p.grp > 0) {
+    int w2 = 1;
+    while (w2 < p.urec_words) w2 <<= 1;
+    p.urec_words = w2;
+    p.n_grp = (n_tiles + p.grp - 1) / p.grp;
+    for (size_t i = p.n_heavy32; i < heavy_rows.size(); ++i) {
+      const int32_t r = heavy_rows[i];
+      const int64_t cr = col_tr[p.row_song[r]];
+      // lanes per listener: ~6 entries of the group per lane
+      int glog = walk_glog(cr > 0 ? (p.row_reads[r] - cr) / cr * p.grp / n_tiles : 0);
+      // rows under kCoocBigRow listeners: every listener held by a lane
+      // group for the whole row (cooc_group_pipelined)
+      if ((int)i >= p.n_heavy32 + p.n_big16)
+        while (glog > 0 && cr > (int64_t)(p.group_nt >> glog) * kGroupPipeR) --glog;
+      p.row_slots[r] = glog << kLightGlogShift;
+    }
+  } else {
+    p.urec_words = 0;
+  }
+  p.pool_cap = mr_par::exclusive_scan(p.row_base.data(), nr);
+  p.row_base[nr] = p.pool_cap;
+}
+
+// The per-(row, listener) record tables built beside the pool: lrec (the u16
+// heavy rows' listeners, lrec_words each: base + (n_grp + 1) u16 starts, a
+// power of 2 of words) and llrec (8 B per light-row listener).
+void cooc_records(const CoocIn& in, CoocPlan& p) {
+  if (p.grp > 0) {
+    for (size_t i = p.n_heavy32; i < p.heavy_rows.size(); ++i) p.n_lrec += in.col_tr[p.row_song[p.heavy_rows[i]]];
+    p.lrec_words = 1;
+    while (2 * (p.lrec_words - 1) < p.n_grp + 1) p.lrec_words <<= 1;
+  }
+  for (int32_t r : p.light_rows) p.n_llrec += in.col_tr[p.row_song[r]];
+}
+
+// The launch order (heavy rows, then light rows with large tables, then the
+// small-table ones) and the per-row vectors mr_cooc_stats / mr_cooc_bytes read.
+void cooc_finish(const CoocIn& in, CoocPlan& p) {
+  const int n_tiles = in.lp.n_tiles;
+  const auto tier = [&](int32_t r) { return light_tier(p.row_slots[r] & kLightSlotsMask, n_tiles); };
+  std::stable_sort(p.light_rows.begin(), p.light_rows.end(), [&](int32_t x, int32_t y) { return tier(x) < tier(y); });
+  for (int32_t r : p.light_rows) p.n_light_tier[tier(r)]++;
+  const size_t nr = p.row_song.size();
+  for (int64_t x : p.row_reads) p.build_reads += x;
+  p.row_users.assign(nr, 0);
+  for (size_t i = 0; i < (size_t)in.d->te_off[in.d->n_test_users]; ++i)
+    if (p.te_row[i] >= 0) p.row_users[p.te_row[i]]++;
+  p.row_listeners.resize(nr);
+  for (size_t r = 0; r < nr; ++r) p.row_listeners[r] = in.col_tr[p.row_song[r]];
+  p.row_light.assign(nr, 0);
+  for (int32_t r : p.light_rows) p.row_light[r] = 1;
+  p.sat = cooc_sat_opt();
+  p.cooc_nt = cooc_nt_opt();
+  p.route = 2;
+}
+
+// ItemBasedModel route (mr_options.ibm_route): the co-listening plan in *out
+// (route 2), or the default plan (route 1) with the reason in *why when the
+// route was wanted (ibm_route 0 or 2) and is declined. free_b: the device's
+// free bytes.
+int plan_cooc(const CoocIn& in, size_t free_b, int dev_share, CoocPlan* out, const char** why) {
+  *out = CoocPlan{};
+  *why = nullptr;
+  if (!in.lp.wide()) *why = "the wide shape only";
+  else if (in.lp.block_songs > kCoocMaxTile) *why = "song tiles <= 32768";
+  if (in.opt.ibm_route == 1) return MR_OK;
+  CoocPlan p;
+  if (!*why) *why = cooc_rows(in, p);
+  if (!*why) *why = cooc_bounds(in, p);
+  if (!*why) {
+    cooc_split(in, p);
+    for (int64_t r = 0; r < p.n_rows(); ++r)
+      if (p.row_base[r] & 3)
+        return fail(MR_E_STATE, "co-listening index: row %lld starts at word %lld (not 16-B aligned)",
+                    (long long)r, (long long)p.row_base[r]);
+    cooc_records(in, p);
+    // the pool and the record tables (urec alive during the load), against
+    // half the free device memory (the share of it a group's context may use)
+    const double rec_b = 4.0 * (double)p.n_lrec * p.lrec_words + 8.0 * (double)p.n_llrec +
+                         4.0 * (double)in.d->n_train_users * p.urec_words;
+    if ((double)p.pool_cap * 4.0 + rec_b > 0.5 * (double)free_b / std::max(1, dev_share))
+      *why = "a pool within half the free device memory";
+  }
+  if (*why) return MR_OK;
+  cooc_finish(in, p);
+  *out = std::move(p);
+  return MR_OK;
+}
+
+// ---- uploads and allocations, on the context stream --------------------------
+// (The callers' host arrays outlive the copies: mr_load synchronises before it returns.)
+
+// The tables of every shape: CSRs, transpose, scales, the tile-major CSR and
+// the chunked stage 1's boundaries.
+int upload_base(mr_ctx* c, const mr_dataset* d, const TrainIndex& ti, const LaunchPlan& lp, const ScaleTables& sc,
+                const TileCsr& tiles) {
+  const int n_tr = d->n_train_users, n_te = d->n_test_users, n_s = d->n_songs;
+  hipStream_t st = c->stream;
+  int rc;
+  if ((rc = dev_upload(c->tr_off, reinterpret_cast<const long long*>(ti.off.data()), (size_t)n_tr + 1, st))) return rc;
+  if ((rc = dev_upload(c->te_off, reinterpret_cast<const long long*>(d->te_off), (size_t)n_te + 1, st))) return rc;
+  if ((rc = dev_upload(c->te_songs, d->te_songs, (size_t)d->te_off[n_te], st))) return rc;
+  if ((rc = dev_upload(c->trs_off, reinterpret_cast<const long long*>(ti.trs_off.data()), (size_t)n_s + 1, st)))
+    return rc;
+  if ((rc = dev_upload(c->trs_users, ti.trs_users.data(), (size_t)ti.trs_off[n_s], st))) return rc;
+  if ((rc = dev_upload(c->q_song, sc.q_song.data(), sc.q_song.size(), st))) return rc;
+  if ((rc = dev_upload(c->sqrt_c, sc.sqrt_c.data(), sc.sqrt_c.size(), st))) return rc;
+  if (lp.wide() && (rc = dev_upload(c->rsq_c, sc.rsq_c.data(), sc.rsq_c.size(), st))) return rc;
+  if ((rc = dev_upload(c->sqrt_tr, sc.sqrt_tr.data(), sc.sqrt_tr.size(), st))) return rc;
+  if ((rc = dev_upload(c->sqrt_te, sc.sqrt_te.data(), sc.sqrt_te.size(), st))) return rc;
+  if ((rc = dev_upload(c->toff, tiles.toff.data(), tiles.toff.size(), st))) return rc;
+  if ((rc = dev_upload(c->tsongs, tiles.tsongs.data(), tiles.tsongs.size(), st))) return rc;
+  if (!lp.fused() && lp.n_chunks > 1) {
+    // Chunk boundaries of every listener list (sorted by train user), built on
+    // the device from the uploaded transpose: the chunked stage 1 reads its
+    // sub-list bounds instead of searching (n_s x (n_chunks + 1) ints).
+    const int nc1 = lp.n_chunks + 1;
+    const size_t n_sb = (size_t)n_s * nc1;
+    if ((rc = dev_alloc(c->sbound, n_sb))) return rc;
+    const int grid = (int)std::min<size_t>(8192, (n_sb + 255) / 256);
+    hipLaunchKernelGGL(k_sbound, dim3(grid), dim3(256), 0, st, c->trs_off.p, c->trs_users.p, n_s, nc1, lp.chunk,
+                       c->sbound.p);
+    MR_HIP(hipGetLastError());
+  }
+  return MR_OK;
+}
+
+// Fused shape (n_tr <= 4096 and bs <= 65536: both halves fit 16 bits): the
+// packed tile entries, the test-visible songs' listener ranges and weights,
+// and stage 1's walk schedule.
+// (separate / wide shapes: neighbour lists allocated by the first two-hop run, ensure_nbr)
+int upload_fused(mr_ctx* c, const mr_dataset* d, const TrainIndex& ti, const LaunchPlan& lp, const ScaleTables& sc,
+                 const TileCsr& tiles) {
+  const int n_tr = d->n_train_users, n_te = d->n_test_users;
+  const std::vector<int64_t>& trs_off = ti.trs_off;
+  hipStream_t st = c->stream;
+  int rc;
+  std::vector<uint32_t> tpack(tiles.tsongs.size(), 0u);
+  for (size_t t = 0; t < (size_t)lp.n_tiles; ++t)
+    for (int v = 0; v < n_tr; ++v)
+      for (int32_t i = tiles.toff[t * n_tr + v]; i < tiles.toff[t * n_tr + v + 1]; ++i)
+        tpack[i] = ((uint32_t)v << 16) | tiles.tsongs[i];
+  if ((rc = dev_upload(c->tpack, tpack.data(), tpack.size(), st))) return rc;
+  // The songsToUsersMap lookup (MR:232) of every test-visible song, resolved
+  // once: its listener range in trs_users and its ibm weight.
+  const size_t nte = (size_t)d->te_off[n_te];
+  std::vector<int2> rng(std::max<size_t>(1, nte));
+  std::vector<long long> tq(std::max<size_t>(1, nte));
+  for (size_t i = 0; i < nte; ++i) {
+    const int s2 = d->te_songs[i];
+    rng[i] = make_int2((int)trs_off[s2], (int)(trs_off[s2 + 1] - trs_off[s2]));
+    tq[i] = sc.q_song[s2];
+  }
+  if ((rc = dev_upload(c->te_rng, rng.data(), rng.size(), st))) return rc;
+  if ((rc = dev_upload(c->te_q, tq.data(), tq.size(), st))) return rc;
+  // Stage 1's walk schedule: per test user, its (song, listener) entries in
+  // song order as (trs_users index, slot of the song in T(u)) — the segment
+  // each flattened entry falls in, which the kernel otherwise finds per step
+  // by a prefix scan and a binary search. Index metadata like te_rng (it
+  // names positions, not listener ids or weights); skipped past 2^26 entries.
+  std::vector<long long> h_sched_off((size_t)n_te + 1, 0);
+  for (int u = 0; u < n_te; ++u) {
+    long long n = 0;
+    for (long long i = d->te_off[u]; i < d->te_off[u + 1]; ++i) n += rng[(size_t)i].y;
+    h_sched_off[(size_t)u + 1] = h_sched_off[(size_t)u] + n;
+  }
+  const long long n_sched = h_sched_off[(size_t)n_te];
+  if (fused_sched_opt() && n_sched <= (1ll << 26)) {
+    std::vector<uint2> sched(std::max<long long>(1, n_sched));
+    size_t o = 0;
+    for (int u = 0; u < n_te; ++u)
+      for (long long i = d->te_off[u]; i < d->te_off[u + 1]; ++i)
+        for (int e = 0; e < rng[(size_t)i].y; ++e)
+          sched[o++] = make_uint2((unsigned)(rng[(size_t)i].x + e), (unsigned)(i - d->te_off[u]));
+    if ((rc = dev_upload(c->te_sched, sched.data(), sched.size(), st))) return rc;
+    if ((rc = dev_upload(c->sched_off, h_sched_off.data(), h_sched_off.size(), st))) return rc;
+  }
+  return MR_OK;
+}
+
+// The co-listening index's tables: rows, pool, launch order and descriptors,
+// the shard's train rows, and the record tables built on the device
+// (k_llrec; k_urec then k_lrec).
+int upload_cooc(mr_ctx* c, const CoocPlan& p, const TrainIndex& ti, const LaunchPlan& lp, int n_tr) {
+  const int n_tiles = lp.n_tiles, lo = lp.lo;
+  const std::vector<int64_t>& trs_off = ti.trs_off;
+  hipStream_t st = c->stream;
+  int rc;
+  const size_t nr = p.row_song.size();
+  if ((rc = dev_upload(c->row_song, p.row_song.data(), nr, st))) return rc;
+  if ((rc = dev_upload(c->te_row, p.te_row.data(), p.te_row.size(), st))) return rc;
+  if ((rc = dev_upload(c->row_base, reinterpret_cast<const long long*>(p.row_base.data()), nr + 1, st))) return rc;
+  if ((rc = dev_alloc(c->row_nnz, nr))) return rc;
+  if ((rc = dev_alloc(c->seg_off, nr * n_tiles))) return rc;
+  if ((rc = dev_alloc(c->seg_len, nr * n_tiles))) return rc;
+  if ((rc = dev_alloc(c->pool, (size_t)p.pool_cap))) return rc;
+  const size_t n_heavy = p.heavy_rows.size();
+  std::vector<int32_t> order(p.heavy_rows);
+  order.insert(order.end(), p.light_rows.begin(), p.light_rows.end());
+  if ((rc = dev_upload(c->rows_order, order.data(), order.size(), st))) return rc;
+  {
+    std::vector<int4> rd(std::max<size_t>(1, order.size()));
+    int64_t at_lrec = 0, at_llrec = 0;  // the rows' first records, in launch order
+    for (size_t i = 0; i < order.size(); ++i) {
+      const int32_t r = order[i], s2 = p.row_song[r];
+      const int cnt = (int)(trs_off[s2 + 1] - trs_off[s2]);
+      int z = (int)trs_off[s2];  // the first listener in trs_users
+      if (p.grp > 0 && (int)i >= p.n_heavy32 && i < n_heavy) {  // the first record in lrec
+        z = (int)at_lrec;
+        at_lrec += cnt;
+      } else if (i >= n_heavy) {  // a light row: its first range record in llrec
+        z = (int)at_llrec;
+        at_llrec += cnt;
+      }
+      rd[i] = make_int4(r, p.row_slots[r], z, cnt);
+    }
+    if ((rc = dev_upload(c->rdesc, rd.data(), rd.size(), st))) return rc;
+    MR_HIP(hipStreamSynchronize(st));
+  }
+  if ((rc = dev_upload(c->row_slots, p.row_slots.data(), p.row_slots.size(), st))) return rc;
+  if (p.light_rows.empty() && p.grp == 0) return MR_OK;
+  // the shard's train rows, shard-local song ids (k_cooc_light's and
+  // k_cooc_group's input)
+  std::vector<int64_t> so((size_t)n_tr + 1, 0);
+  std::copy(p.shard_deg.begin(), p.shard_deg.begin() + n_tr, so.begin());
+  so[n_tr] = mr_par::exclusive_scan(so.data(), (int64_t)n_tr);
+  // + 4 zero entries: rows_walk's 16-B chunk loads never leave the buffer
+  mr_par::buffer<uint32_t> ss((size_t)so[n_tr] + 4);
+  std::fill(ss.begin() + so[n_tr], ss.end(), 0u);
+  mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
+    for (int64_t v = a; v < b; ++v) {
+      const int32_t* r0 = std::lower_bound(ti.songs.data() + ti.off[v], ti.songs.data() + ti.off[v + 1], lo);
+      for (int64_t i = 0; i < so[v + 1] - so[v]; ++i) ss[so[v] + i] = (uint32_t)(r0[i] - lo);
+    }
+  });
+  if ((rc = dev_upload(c->sr_off, reinterpret_cast<const long long*>(so.data()), so.size(), st))) return rc;
+  if ((rc = dev_upload(c->sr_songs, ss.data(), ss.size(), st))) return rc;
+  if (!p.light_rows.empty()) {  // the light rows' listener ranges
+    if ((rc = dev_alloc(c->llrec, (size_t)std::max<int64_t>(1, p.n_llrec)))) return rc;
+    hipLaunchKernelGGL(k_llrec, dim3((unsigned)p.light_rows.size()), dim3(256), 0, st, c->rdesc.p + n_heavy,
+                       c->row_song.p, c->trs_off.p, c->trs_users.p, c->sr_off.p, c->llrec.p);
+    MR_HIP(hipGetLastError());
+  }
+  if (p.grp > 0) {  // k_cooc_group's records, on the device: per user (tile starts), then per (row, listener)
+    if ((rc = dev_alloc(c->urec, (size_t)std::max(1, n_tr) * p.urec_words))) return rc;
+    hipLaunchKernelGGL(k_urec, dim3((std::max(1, n_tr) + 255) / 256), dim3(256), 0, st, c->sr_off.p,
+                       c->sr_songs.p, n_tr, n_tiles, lp.block_songs, p.urec_words, c->urec.p);
+    MR_HIP(hipGetLastError());
+    if ((rc = dev_alloc(c->lrec, (size_t)std::max<int64_t>(1, p.n_lrec) * p.lrec_words))) return rc;
+    const int n16 = (int)n_heavy - p.n_heavy32;
+    if (n16 > 0)
+      hipLaunchKernelGGL(k_lrec, dim3(n16), dim3(256), 0, st, c->rdesc.p + p.n_heavy32, c->row_song.p,
+                         c->trs_off.p, c->trs_users.p, c->urec.p, p.urec_words, n_tiles, p.grp, p.n_grp, p.lrec_words,
+                         c->lrec.p);
+    MR_HIP(hipGetLastError());
+    MR_HIP(hipStreamSynchronize(st));
+    c->urec.release();  // (lrec holds what the runs need)
+  }
+  MR_HIP(hipStreamSynchronize(st));  // so / ss die here
+  return MR_OK;
+}
+
+// Candidate and top-k lists, counters, the dense model and the flag word.
+int alloc_outputs(mr_ctx* c, const LaunchPlan& lp, int route, int n_te) {
+  hipStream_t st = c->stream;
+  const int k = lp.k;
+  int rc;
+  if (k > 0) {
+    // wide: per-tile candidates of one launch (a neighbour batch; the
+    // co-listening route launches up to 65528 users at once)
+    const int cand_users = !lp.wide() ? n_te : route == 2 ? std::max(lp.batch, std::min(n_te, 65528)) : lp.batch;
+    const size_t nc = (size_t)cand_users * lp.n_tiles * k;
+    if ((rc = dev_alloc(c->cand_key, nc))) return rc;
+    if ((rc = dev_alloc(c->cand_song, nc))) return rc;
+    // keys then songs in ONE record block: the send buffer of the song-shard
+    // exchange (one all-gather of rec bytes per shard, mr_topk_merge_records_async)
+    const size_t nk = (size_t)n_te * k;
+    if ((rc = dev_alloc(c->top_key, (size_t)topk_record_bytes(nk) / 8))) return rc;
+    c->top_song.p = reinterpret_cast<int*>(c->top_key.p + nk);
+    c->top_song.n = nk;
+    c->top_song.own = false;
+    if ((rc = dev_alloc(c->top_score, (size_t)n_te * k))) return rc;
+    // (the in-launch hand-off's per-user counters, one line each: fused / separate shapes only)
+    const size_t n_ctr = lp.wide() ? (size_t)n_te : (size_t)n_te * kCounterStride;
+    if ((rc = dev_alloc(c->counter, n_ctr))) return rc;
+    MR_HIP(hipMemsetAsync(c->counter.p, 0, n_ctr * sizeof(unsigned), st));
+  }
+  const size_t esz = c->opt.out_dtype == MR_OUT_F64 ? 8 : 4;
+  if ((rc = dev_alloc(c->dense, c->opt.dense ? (size_t)n_te * lp.width * esz : 1))) return rc;
+  if ((rc = dev_alloc(c->flag, 1))) return rc;
+  return MR_OK;
+}
+
+// The kernels of the load's shape and route (c->shape, c->cooc), their
+// dynamic LDS sizes and every kernel's LDS attribute.
+int setup_kernels(mr_ctx* c, const LaunchPlan& lp, int n_tr) {
+  const CoocPlan& p = c->cooc;
+  const int bs = lp.block_songs, k = lp.k, n_chunks = lp.n_chunks;
+  const bool fused = lp.fused(), wide = lp.wide();
+  {  // the candidate-only tile top-k (wide_cand_topk): top-k-only wide runs
+    const char* e = std::getenv("MR_WIDE_CAND");
+    const int nt = p.route == 2 ? p.cooc_nt : kWideThreads;  // the scoring kernel's threads
+    c->cand_on = wide && !c->opt.dense && k >= 1 && k <= nt / 16 && !c->opt.topk_lists && bs <= kCandE * nt &&
+                 !(e && e[0] == '0');
+  }
+  c->wide_lds = wide ? (size_t)wide_lds<kWideThreads>(bs, k, n_chunks).total : 0;
+  pick_kernels<MR_UBM>(c);
+  pick_kernels<MR_IBM>(c);
+  c->score_lds = wide ? c->wide_lds
+                      : (size_t)score_lds(bs, fused ? n_tr : 0, k, lp.n_tiles, fused ? 0 : n_chunks).total;
+  if (c->score_lds > 160 * 1024)
+    return fail(MR_E_INVALID, "scoring kernel needs %zu B of LDS (> 160 KiB): lower block_songs or topk",
+                c->score_lds);
+  c->nbr_lds = (size_t)align16(lp.chunk * 8) + kThreads * 16 + (kThreads + 4 + kWaves) * 4;
+  for (int m = 0; m < 2; ++m) {
+    MR_HIP(hipFuncSetAttribute((const void*)c->score_kernel[m], hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)c->score_lds));
+    MR_HIP(hipFuncSetAttribute((const void*)c->nbr_kernel[m], hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)c->nbr_lds));
+  }
+  if (p.route == 2) {
+    // the score kernel's row descriptors (40 B each: sparse + dense views) in its top-k scratch
+    const WideLds<kWideThreads> WL = p.cooc_nt == 512 ? wide_lds<512>(bs, k, n_chunks).as_wide()
+                                                      : wide_lds<kWideThreads>(bs, k, n_chunks);
+    c->cooc_score_lds = (size_t)WL.total;
+    // (<= 255 per pass: the scoring packs a pass's entry and dense-row prefix sums in one int)
+    c->nseg = std::min(std::min(p.cooc_nt, (WL.total - WL.wk - 8) / 40), 255);
+    if (c->nseg < 16) return fail(MR_E_INVALID, "co-listening route: no LDS for row descriptors");
+    c->cooc_lds = (size_t)cooc_build_lds<false>(bs);
+    if (p.grp > 0)
+      MR_HIP(hipFuncSetAttribute(p.group_nt == 512 ? (const void*)k_cooc_group<512> : (const void*)k_cooc_group<1024>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, cooc_group_lds(bs, p.grp)));
+    for (int t = 0; t < kLightTiers; ++t)
+      if (int rc2 = light_tier_call(t, nullptr, 0, nullptr, CoocParams{})) return rc2;
+    MR_HIP(hipFuncSetAttribute((const void*)c->cooc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)c->cooc_score_lds));
+    MR_HIP(hipFuncSetAttribute((const void*)k_cooc_build<MR_COOC_NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)c->cooc_lds));
+    MR_HIP(hipFuncSetAttribute((const void*)k_cooc_build<MR_COOC_NT16, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               cooc_build_lds<true>(bs)));
+  }
+  if (wide && k > 0) {
+    c->merge_lds = (size_t)merge_lds_bytes(k);
+    MR_HIP(hipFuncSetAttribute((const void*)k_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)c->merge_lds));
+  }
+  return MR_OK;
+}
+
+}  // namespace
+
 
 extern "C" {
 
@@ -4459,672 +5234,62 @@ int mr_load(mr_ctx* c, const mr_dataset* d) {
   std::vector<int32_t> col_tr;
   int rc;
   if ((rc = check_dataset(d, col_tr))) return rc;
-  const int64_t nnz_tr = d->tr_off[n_tr];
-  const int W = (int)std::max<int64_t>(1, std::min<int64_t>(mr_par::usable_cores(), nnz_tr >> 18));
-  std::vector<int64_t> trs_off((size_t)n_s + 1, 0);
-  for (int s2 = 0; s2 < n_s; ++s2) trs_off[s2 + 1] = trs_off[s2] + col_tr[s2];
+  // the plans below budget against the free device memory (the context's own data is released)
+  size_t free_b = 0, total_b = 0;
+  MR_HIP(hipMemGetInfo(&free_b, &total_b));
+  LaunchPlan lp;
+  if ((rc = plan_launch(c->opt, n_tr, n_te, n_s, free_b, c->dev_share, lp))) return rc;
+
+  // host side: the train index, the scale tables, the tile-major CSR, the route
+  TrainIndex ti;
+  ti.W = (int)std::max<int64_t>(1, std::min<int64_t>(mr_par::usable_cores(), d->tr_off[n_tr] >> 18));
+  ti.trs_off.assign((size_t)n_s + 1, 0);
+  for (int s2 = 0; s2 < n_s; ++s2) ti.trs_off[s2 + 1] = ti.trs_off[s2] + col_tr[s2];
   trace("counts");
-  // Train users renumbered by distinct-song count, descending (ties by id),
-  // unless opt.train_order = 1: the users of one wave then have segments of
-  // similar length in every song tile, so no lane waits on one heavy
-  // listener's long tail (heavy listeners dominate every neighbourhood).
-  // Results do not change: every accumulation is an order-free integer sum
-  // and the outputs are indexed by test user and song only. (A stable
-  // counting sort by degree.)
-  std::vector<int32_t> perm(std::max(1, n_tr));  // new id -> caller's id
-  if (c->opt.train_order == 0 && n_tr > 0) {
-    int64_t max_deg = 0;
-    for (int v = 0; v < n_tr; ++v) max_deg = std::max(max_deg, d->tr_off[v + 1] - d->tr_off[v]);
-    std::vector<int64_t> at((size_t)max_deg + 1, 0);
-    for (int v = 0; v < n_tr; ++v) at[max_deg - (d->tr_off[v + 1] - d->tr_off[v])]++;
-    int64_t run = 0;
-    for (auto& x : at) { const int64_t n = x; x = run; run += n; }
-    for (int v = 0; v < n_tr; ++v) perm[at[max_deg - (d->tr_off[v + 1] - d->tr_off[v])]++] = v;
-  } else {
-    for (int v = 0; v < n_tr; ++v) perm[v] = v;
-  }
-  std::vector<int64_t> p_off((size_t)n_tr + 1, 0);
-  mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
-    for (int64_t v = a; v < b; ++v) p_off[v] = d->tr_off[perm[v] + 1] - d->tr_off[perm[v]];
-  });
-  p_off[n_tr] = mr_par::exclusive_scan(p_off.data(), (int64_t)n_tr);
-  mr_par::buffer<int32_t> p_songs((size_t)std::max<int64_t>(1, nnz_tr));
-  std::vector<int32_t> p_len(std::max(1, n_tr));
-  mr_par::parallel_dynamic(n_tr, 2048, [&](int64_t v, int) {
-    const int o = perm[v];
-    std::copy(d->tr_songs + d->tr_off[o], d->tr_songs + d->tr_off[o + 1], p_songs.begin() + p_off[v]);
-    p_len[v] = d->tr_len[o];
-  });
-  const int64_t* tr_off = p_off.data();
-  const int32_t* tr_songs = p_songs.data();
-  const int32_t* tr_len = p_len.data();
+  renumber_train(d, c->opt.train_order, ti);
   trace("renumber");
-  // Transpose song -> train users, lists ascending in v: worker w owns a
-  // contiguous range of (new) users and a private cursor per song.
-  const std::vector<int64_t> ucut = weighted_cuts(tr_off, n_tr, W);
-  mr_par::buffer<int32_t> trs_users((size_t)std::max<int64_t>(1, trs_off[n_s]));
-  {
-    std::vector<std::vector<int64_t>> pos(W);
-    mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
-      for (int64_t w = w0; w < w1; ++w) {
-        pos[w].assign(n_s, 0);
-        for (int64_t i = tr_off[ucut[w]]; i < tr_off[ucut[w + 1]]; ++i) pos[w][tr_songs[i]]++;
-      }
-    }, 1, W);
-    mr_par::parallel_for(n_s, [&](int64_t a, int64_t b, int) {
-      for (int64_t s2 = a; s2 < b; ++s2) {
-        int64_t at = trs_off[s2];
-        for (int w = 0; w < W; ++w) {
-          const int64_t n = pos[w][s2];
-          pos[w][s2] = at;
-          at += n;
-        }
-      }
-    }, 4096);
-    mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
-      for (int64_t w = w0; w < w1; ++w)
-        for (int64_t v = ucut[w]; v < ucut[w + 1]; ++v)
-          for (int64_t i = tr_off[v]; i < tr_off[v + 1]; ++i) trs_users[pos[w][tr_songs[i]]++] = (int32_t)v;
-    }, 1, W);
-  }
+  transpose_train(n_tr, n_s, ti);
   trace("transpose");
-  // Shard geometry and launch shape.
-  const int lo = c->opt.song_lo, hi = c->opt.song_hi > 0 ? c->opt.song_hi : n_s;
-  if (lo < 0 || hi > n_s || lo >= hi) return fail(MR_E_INVALID, "song shard [%d,%d) invalid for %d songs", lo, hi, n_s);
-  const int width = hi - lo;
-  const int k = c->opt.topk;
-  const int shape = pick_shape(c->opt, n_tr, n_te);
-  const bool fused = shape == kShapeFused, wide = shape == kShapeWide;
-  if (wide && k > kMaxTopkLarge)
-    return fail(MR_E_INVALID, "wide shape keeps topk <= %d (got %d)", kMaxTopkLarge, k);
-  if (fused && n_tr > kMaxFusedTrainUsers)
-    return fail(MR_E_INVALID, "fused stage 1 needs n_train_users <= %d (got %d)", kMaxFusedTrainUsers, n_tr);
-  // Stage 1 of the separate / wide shapes: one LDS chunk of train users per workgroup.
-  const int chunk = stage1_chunk_for(c->opt, n_tr);
-  if ((n_tr + chunk - 1) / chunk > kMaxChunks)
-    return fail(MR_E_INVALID, "stage1_chunk %d gives more than %d chunks", chunk, kMaxChunks);
-  const int n_chunks = (std::max(1, n_tr) + chunk - 1) / chunk;
-  int bs;
-  if (wide) {
-    // the widest tile the LDS holds (every tile re-walks the user's whole
-    // neighbour list), then balanced: n_tiles = ceil(width / max), bs =
-    // ceil(width / n_tiles) rounded up to 256
-    const int bmax = wide_bmax(k, n_chunks);
-    const long long nt = ((long long)width + bmax - 1) / bmax;
-    bs = c->opt.block_songs > 0 ? c->opt.block_songs
-                                : (int)std::min<long long>(bmax, (((long long)width + nt - 1) / nt + 255) / 256 * 256);
-    if (wide_lds<kWideThreads>(bs, k, n_chunks).total > kLdsBytes)
-      return fail(MR_E_INVALID, "wide shape: block_songs %d needs more than %d B of LDS", bs, kLdsBytes);
-  } else {
-    bs = c->opt.block_songs > 0 ? c->opt.block_songs : auto_block_songs(width, n_te, fused, k, n_tr);
-  }
-  if (fused && bs > 8192) return fail(MR_E_INVALID, "fused stage 1 needs block_songs <= 8192 (got %d)", bs);
-  if (!wide && k > kMaxTopkLarge && bs > kMaxTopkTile)
-    return fail(MR_E_INVALID, "with topk > %d block_songs must be <= %d (got %d)", kMaxTopkLarge, kMaxTopkTile, bs);
-  const int n_tiles = (width + bs - 1) / bs;
-  // Per-song / per-user fixed-point tables, computed once on the host with
-  // correctly rounded std::sqrt (java.lang.Math.sqrt semantics, MR:147/237).
-  const int F = c->opt.frac_bits;
-  const double two_f = std::ldexp(1.0, F);
-  std::vector<double> sqrt_c(n_s), sqrt_tr(std::max(1, n_tr)), sqrt_te(n_te);
-  std::vector<long long> q_song(n_s);
-  std::vector<float> rsq_c(n_s);
-  mr_par::parallel_for(n_s, [&](int64_t a, int64_t b, int) {
-    for (int64_t s2 = a; s2 < b; ++s2) {
-      sqrt_c[s2] = std::sqrt((double)d->song_count[s2]);
-      q_song[s2] = (long long)std::nearbyint(two_f / sqrt_c[s2]);
-      rsq_c[s2] = sqrt_c[s2] > 0.0 ? (float)(1.0 / sqrt_c[s2]) : 0.f;
-    }
-  });
-  mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
-    for (int64_t v = a; v < b; ++v) sqrt_tr[v] = std::sqrt((double)tr_len[v]);
-  });
-  for (int u = 0; u < n_te; ++u) sqrt_te[u] = std::sqrt((double)d->te_len[u]);
-  // Tile-major train CSR over the shard's songs: for tile t, user v, the
-  // tile-local ids of S(v) ∩ [lo + t*bs, lo + (t+1)*bs) live at
-  // tsongs[toff[t*n_tr + v] .. toff[t*n_tr + v + 1]) (entries ordered by
-  // (tile, user, song)), so neighbouring users' segments share cache lines.
-  // Every user writes only its own (tile, user) slots: parallel over users.
-  const size_t n_tv = (size_t)n_tiles * n_tr;
-  mr_par::buffer<int32_t> toff(n_tv + 1);
-  mr_par::parallel_for((int64_t)n_tv, [&](int64_t a, int64_t b, int) { std::fill(toff.begin() + a, toff.begin() + b, 0); });
-  mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
-    for (int64_t w = w0; w < w1; ++w)
-      for (int64_t v = ucut[w]; v < ucut[w + 1]; ++v)
-        for (int64_t i = tr_off[v]; i < tr_off[v + 1]; ++i) {
-          const int s2 = tr_songs[i];
-          if (s2 >= lo && s2 < hi) toff[(size_t)((s2 - lo) / bs) * n_tr + v]++;
-        }
-  }, 1, W);
-  const int64_t n_entries = mr_par::exclusive_scan(toff.data(), (int64_t)n_tv);
-  toff[n_tv] = (int32_t)n_entries;
-  // padded to whole 8-B words (+1): the wide kernel loads a segment's ids as
-  // aligned 4-id words
-  mr_par::buffer<uint16_t> tsongs((std::max<int64_t>(1, n_entries) + 3) / 4 * 4 + 4);
-  std::fill(tsongs.begin() + n_entries, tsongs.end(), (uint16_t)0);
-  mr_par::parallel_for(W, [&](int64_t w0, int64_t w1, int) {
-    for (int64_t w = w0; w < w1; ++w)
-      for (int64_t v = ucut[w]; v < ucut[w + 1]; ++v) {
-        int cur_t = -1;
-        int32_t at = 0;
-        for (int64_t i = tr_off[v]; i < tr_off[v + 1]; ++i) {  // songs ascend, so tiles do
-          const int s2 = tr_songs[i];
-          if (s2 < lo || s2 >= hi) continue;
-          const int t = (s2 - lo) / bs;
-          if (t != cur_t) {
-            cur_t = t;
-            at = toff[(size_t)t * n_tr + v];
-          }
-          tsongs[at++] = (uint16_t)(s2 - lo - t * bs);
-        }
-      }
-  }, 1, W);
+  const ScaleTables scales = make_scales(d, ti, c->opt.frac_bits);
+  TileCsr tiles;
+  build_tiles(ti, lp, n_tr, tiles);
   trace("tiles");
-  // Separate / wide shapes: test-user batches so the neighbour lists fit 8 GiB.
-  const int cap = n_chunks * chunk;
-  // one launch's neighbour lists (batch x cap x 12 B): an eighth of the free
-  // device memory, 8-32 GiB (C5's 2,000 users in one launch on a 288 GB
-  // MI355X; allocated at the first two-hop run, ensure_nbr)
-  size_t free_b0 = 0, total_b0 = 0;
-  MR_HIP(hipMemGetInfo(&free_b0, &total_b0));
-  const size_t budget = std::min<size_t>((size_t)32 << 30, std::max<size_t>((size_t)8 << 30, free_b0 / 8)) /
-                        (size_t)std::max(1, c->dev_share);
-  const int batch = fused ? n_te
-                          : (int)std::max<size_t>(1, std::min<size_t>(std::min(n_te, 65528),
-                                                                      budget / ((size_t)cap * 12)));
+  CoocPlan plan;
+  const char* why = nullptr;
+  if ((rc = plan_cooc(CoocIn{d, c->opt, ti, lp, col_tr}, free_b, c->dev_share, &plan, &why))) return rc;
+  if (c->opt.ibm_route == 2 && why)
+    return fail(MR_E_INVALID, "ibm_route 2 (co-listening index) needs %s", why);
+  trace("route");
 
-  // ItemBasedModel route (mr_options.ibm_route). The co-listening index has
-  // one row per distinct test-visible song with train listeners, heaviest
-  // first; row r's pool range holds at most min(width, Σ_{v ∈ L_tr(s2)}
-  // |S(v) ∩ shard|) entries (its non-zero counts over the shard's songs).
-  int route = 1;
-  std::vector<int32_t> row_song, te_row;
-  std::vector<int64_t> row_base;
-  std::vector<int32_t> heavy_rows, light_rows, row_slots;
-  int dense_div = kCoocDenseDiv;
-  int n_heavy32 = 0, n_big16 = 0, tcap16 = 0, tcap32 = 0;
-  int32_t max_shard_deg = 0;
-  int grp = 0, n_grp = 0, urec_words = 0, lrec_words = 0;  // k_cooc_group (0: the per-tile k_cooc_build)
-  std::vector<int64_t> row_reads;
-  int64_t pool_cap = 0;
-  {
-    const char* why = nullptr;
-    int32_t max_c = 0;
-    if (!wide) why = "the wide shape only";
-    else if (bs > kCoocMaxTile) why = "song tiles <= 32768";
-    if (!why && c->opt.ibm_route != 1) {
-      const int64_t nte = d->te_off[n_te];
-      std::vector<int32_t> row_of(n_s, -1);
-      for (int64_t i = 0; i < nte; ++i) {
-        const int s2 = d->te_songs[i];
-        if (col_tr[s2] > 0 && row_of[s2] < 0) { row_of[s2] = 0; row_song.push_back(s2); }
-      }
-      std::sort(row_song.begin(), row_song.end(), [&](int x, int y) {
-        return col_tr[x] != col_tr[y] ? col_tr[x] > col_tr[y] : x < y;
-      });
-      for (size_t r = 0; r < row_song.size(); ++r) {
-        row_of[row_song[r]] = (int32_t)r;
-        max_c = std::max(max_c, col_tr[row_song[r]]);
-      }
-      te_row.resize(std::max<int64_t>(1, nte));
-      for (int64_t i = 0; i < nte; ++i) te_row[i] = row_of[d->te_songs[i]];
-      if (max_c > (int32_t)kCoocCntMask) why = "train listener counts < 131072";
-      // the row descriptors hold 32-bit listener-list starts and k_urec's
-      // records 32-bit shard-row bases (shard entries <= train entries)
-      else if (trs_off[n_s] >= (int64_t)INT32_MAX) why = "train entries < 2^31";
-      else if ((long long)row_song.size() * n_tiles > INT32_MAX) why = "rows x tiles < 2^31";
-    }
-    if (!why && c->opt.ibm_route != 1) {
-      // |S(v) ∩ [lo, hi)| of every (renumbered) train user, then the row bounds
-      std::vector<int32_t> deg((size_t)std::max(1, n_tr));
-      mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
-        for (int64_t v = a; v < b; ++v) {
-          const int32_t* r0 = tr_songs + tr_off[v];
-          const int32_t* r1 = tr_songs + tr_off[v + 1];
-          deg[v] = (int32_t)(std::lower_bound(r0, r1, hi) - std::lower_bound(r0, r1, lo));
-        }
-      });
-      for (int v = 0; v < n_tr; ++v) max_shard_deg = std::max(max_shard_deg, deg[v]);
-      const int64_t nr = (int64_t)row_song.size();
-      row_base.assign((size_t)nr + 1, 0);
-      row_reads.assign((size_t)nr, 0);
-      mr_par::parallel_for(nr, [&](int64_t a, int64_t b, int) {
-        for (int64_t r = a; r < b; ++r) {
-          const int s2 = row_song[r];
-          int64_t sum = 0;
-          for (int64_t i = trs_off[s2]; i < trs_off[s2 + 1]; ++i) sum += deg[trs_users[i]];
-          row_reads[r] = (trs_off[s2 + 1] - trs_off[s2]) + sum;
-          row_base[r] = std::min<int64_t>(sum, width);  // the row's non-zeros: its sparse bound
-        }
-      }, 256);
-      // auto: the cost model of cooc_pays (the rows' bounds = sparse entry bounds here)
-      if (c->opt.ibm_route == 0) {
-        double e_est = 0.0;
-        for (int64_t i = 0; i < d->te_off[n_te]; ++i)
-          if (te_row[i] >= 0) e_est += (double)row_base[te_row[i]];
-        double v_est = 0.0;
-        for (int u = 0; u < n_te; ++u) {
-          double sc = 0.0;
-          for (int64_t i = d->te_off[u]; i < d->te_off[u + 1]; ++i) sc += col_tr[d->te_songs[i]];
-          v_est += std::min<double>(sc, n_tr);
-        }
-        if (!cooc_pays(v_est * n_tiles, e_est, row_base, row_reads, row_song, col_tr, n_tiles))
-          why = "a cheaper estimate than the two-hop route (auto)";
-      }
-    }
-    if (!why && c->opt.ibm_route != 1) {
-      // light rows (k_cooc_light): the bound fits half the hash slots
-      const int64_t nr = (int64_t)row_song.size();
-      const bool light_ok = width <= kLightMaxWidth && n_tiles <= kLightMaxTiles && cooc_light_opt();
-      // a light row's table: the smallest power of 2 of at least bound * 100 / lload slots (the
-      // entry bound at most lload % of the slots), at most light_slots_max (MR_COOC_LIGHT_MAX /
-      // MR_COOC_LIGHT_LOAD: A/B knobs; defaults 32768 slots, 80 %)
-      // narrow shard: the group kernel would hold every tile in one pass
-      // (the conditions of its set-up below, before the heavy rows are known)
-      bool narrow = false;
-      if (cooc_group_opt() && 1 + (n_tiles + 2) / 2 <= 32 && max_shard_deg <= 65535 &&
-          n_tiles <= std::min(kMaxGroupTiles, cooc_group_max_opt()))
-        narrow = cooc_group_lds(bs, n_tiles) <= kLdsBytes;
-      const int64_t lload = cooc_light_load_opt(), light_slots_max = cooc_light_max_opt(narrow);
-      dense_div = cooc_dense_div_opt();
-      // a dense segment holds whole interleaved blocks (cooc_dense_words):
-      // the words past its songs' bytes, over every tile, on each heavy row's bound
-      int64_t dense_pad = 0;
-      for (int t = 0; t < n_tiles; ++t) {
-        const int bw = (int)(std::min<int64_t>(width, (int64_t)(t + 1) * bs) - (int64_t)t * bs);
-        dense_pad += cooc_dense_words(bw) - (bw + 3) / 4;
-      }
-      // whole 16-B words: every row's bound stays a multiple of 4 words, so
-      // every row (placed by the exclusive scan below) starts 16-B aligned for
-      // the scorer's dvec_t loads and k_cooc_group's chunk_t stores
-      dense_pad = (dense_pad + 3) & ~(int64_t)3;
-      row_slots.assign((size_t)std::max<int64_t>(1, nr), 0);
-      for (int64_t r = 0; r < nr; ++r) {
-        if (light_ok && row_base[r] * 100 <= light_slots_max * lload && col_tr[row_song[r]] <= (int32_t)kLightCntMask) {
-          int sl = 1024;
-          while ((int64_t)sl * lload < row_base[r] * 100) sl <<= 1;
-          row_slots[r] = sl;
-          // lanes per listener of rows_walk: the largest power of 2 G <= 16
-          // with 6 G <= the row's shard entries per listener (>= 6 per lane)
-          const int64_t c = col_tr[row_song[r]];
-          const int64_t per = c > 0 ? (row_reads[r] - c) / c : 0;
-          int glog = 0;
-          while (glog < 4 && ((int64_t)6 << (glog + 1)) <= per) ++glog;
-          row_slots[r] |= glog << kLightGlogShift;
-          light_rows.push_back((int32_t)r);
-          row_base[r] = (row_base[r] + 3) & ~(int64_t)3;
-        } else {
-          // k_cooc_build: a tile's segment is sparse (its non-zeros) or dense
-          // (<= kCoocDenseDiv x its non-zeros, <= the tile's songs), in whole
-          // 16-B words (32-B for u32 counts)
-          // (dense: count bytes <= kCoocDenseDiv / 4 x the non-zeros, + excess entries <= the non-zeros)
-          const int64_t nz = row_base[r];
-          const int64_t dn = std::max<int64_t>(1, std::min<int64_t>(dense_div, width)) * nz;
-          row_base[r] = ((std::min<int64_t>(width, dn) + nz + 3) & ~(int64_t)3) + 8 * (int64_t)n_tiles + dense_pad;
-          heavy_rows.push_back((int32_t)r);
-        }
-      }
-      // heavy rows whose counts may pass 65535 first (u32 counters), the rest
-      // keep their order (u16-pair counters, k_cooc_build<.., true>)
-      const bool all32 = !MR_COOC_P16 || cooc_dense32_opt();
-      std::stable_partition(heavy_rows.begin(), heavy_rows.end(), [&](int32_t r) {
-        return all32 || col_tr[row_song[r]] >= 65536;
-      });
-      for (int32_t r : heavy_rows) n_heavy32 += (all32 || col_tr[row_song[r]] >= 65536) ? 1 : 0;
-      // Big rows (>= kCoocBigRow listeners, and every u32 row): one workgroup
-      // per (row, tile), each tile a fixed slot of tcap words (the larger of a
-      // dense segment and the longest sparse one), so the row's tiles run in
-      // parallel. Rows are heaviest first, so the big rows of each kind lead.
-      const int sparse_max = dense_div > 0 ? (bs + dense_div - 1) / dense_div : bs;
-      // a dense segment: the count bytes + at most one excess entry per song
-      tcap32 = (std::max(sparse_max, cooc_dense_words(bs) + bs) + 7) & ~7;
-      tcap16 = tcap32;
-      n_big16 = 0;
-      for (size_t i = n_heavy32; i < heavy_rows.size(); ++i) {
-        if (col_tr[row_song[heavy_rows[i]]] < kCoocBigRow) break;
-        n_big16++;
-      }
-      for (size_t i = 0; i < heavy_rows.size(); ++i)
-        if ((int)i < n_heavy32 + n_big16)
-          row_base[heavy_rows[i]] = (int64_t)n_tiles * ((int)i < n_heavy32 ? tcap32 : tcap16);
-      // The u16 heavy rows by tile groups (k_cooc_group) when the per-user
-      // records fit (one 128-B line: n_tiles <= 61, u16 starts: shard rows
-      // < 65536 songs): the widest group whose counters fit the LDS.
-      urec_words = 1 + (n_tiles + 2) / 2;
-      if (cooc_group_opt() && (int)heavy_rows.size() > n_heavy32 && urec_words <= 32 && max_shard_deg <= 65535) {
-        grp = std::min(std::min(n_tiles, kMaxGroupTiles), cooc_group_max_opt());
-        while (grp > 0 && cooc_group_lds(bs, grp) > kLdsBytes) --grp;
-      }
-      if (grp > 0) {
-        int w2 = 1;
-        while (w2 < urec_words) w2 <<= 1;
-        urec_words = w2;
-        n_grp = (n_tiles + grp - 1) / grp;
-        // lanes per listener of rows_walk: ~6 entries of the group per lane
-        for (size_t i = n_heavy32; i < heavy_rows.size(); ++i) {
-          const int32_t r = heavy_rows[i];
-          const int64_t cr = col_tr[row_song[r]];
-          const int64_t per = cr > 0 ? (row_reads[r] - cr) / cr * grp / n_tiles : 0;
-          int glog = 0;
-          while (glog < 4 && ((int64_t)6 << (glog + 1)) <= per) ++glog;
-          // rows under kCoocBigRow listeners: every listener held by a lane
-          // group for the whole row (cooc_group_pipelined)
-          if ((int)i >= n_heavy32 + n_big16)
-            while (glog > 0 && cr > (int64_t)(cooc_group_nt_opt() >> glog) * kGroupPipeR) --glog;
-          row_slots[r] = glog << kLightGlogShift;
-        }
-      } else {
-        urec_words = 0;
-      }
-      pool_cap = mr_par::exclusive_scan(row_base.data(), nr);
-      row_base[nr] = pool_cap;
-      for (int64_t r = 0; r < nr; ++r)
-        if (row_base[r] & 3)
-          return fail(MR_E_STATE, "co-listening index: row %lld starts at word %lld (not 16-B aligned)",
-                      (long long)r, (long long)row_base[r]);
-      // the pool and the per-(row, listener) record tables built beside it:
-      // lrec (the u16 heavy rows' listeners, lrec_words each), llrec (8 B per
-      // light-row listener) and urec (alive during the load), against half the
-      // free device memory (the share of it a group's context may use)
-      double rec_b = 0.0;
-      {
-        int64_t n_lrec = 0, n_llrec = 0;
-        for (size_t i = 0; i < heavy_rows.size(); ++i)
-          if (grp > 0 && (int)i >= n_heavy32) n_lrec += col_tr[row_song[heavy_rows[i]]];
-        for (int32_t r : light_rows) n_llrec += col_tr[row_song[r]];
-        int lw = 1;
-        const int ng = grp > 0 ? (n_tiles + grp - 1) / grp : 0;
-        while (2 * (lw - 1) < ng + 1) lw <<= 1;
-        rec_b = 4.0 * (double)n_lrec * lw + 8.0 * (double)n_llrec + 4.0 * (double)n_tr * urec_words;
-      }
-      size_t free_b = 0, total_b = 0;
-      MR_HIP(hipMemGetInfo(&free_b, &total_b));
-      if ((double)pool_cap * 4.0 + rec_b > 0.5 * (double)free_b / std::max(1, c->dev_share))
-        why = "a pool within half the free device memory";
-    }
-    if (c->opt.ibm_route == 2 && why)
-      return fail(MR_E_INVALID, "ibm_route 2 (co-listening index) needs %s", why);
-    route = (c->opt.ibm_route != 1 && !why) ? 2 : 1;
-    trace("route");
-  }
-
-  hipStream_t st = c->stream;
-  if ((rc = dev_upload(c->tr_off, reinterpret_cast<const long long*>(tr_off), (size_t)n_tr + 1, st))) return rc;
-  if ((rc = dev_upload(c->te_off, reinterpret_cast<const long long*>(d->te_off), (size_t)n_te + 1, st))) return rc;
-  if ((rc = dev_upload(c->te_songs, d->te_songs, (size_t)d->te_off[n_te], st))) return rc;
-  if ((rc = dev_upload(c->trs_off, reinterpret_cast<const long long*>(trs_off.data()), trs_off.size(), st))) return rc;
-  if ((rc = dev_upload(c->trs_users, trs_users.data(), (size_t)trs_off[n_s], st))) return rc;
-  if ((rc = dev_upload(c->q_song, q_song.data(), q_song.size(), st))) return rc;
-  if ((rc = dev_upload(c->sqrt_c, sqrt_c.data(), sqrt_c.size(), st))) return rc;
-  if (wide && (rc = dev_upload(c->rsq_c, rsq_c.data(), rsq_c.size(), st))) return rc;
-  if ((rc = dev_upload(c->sqrt_tr, sqrt_tr.data(), sqrt_tr.size(), st))) return rc;
-  if ((rc = dev_upload(c->sqrt_te, sqrt_te.data(), sqrt_te.size(), st))) return rc;
-  if ((rc = dev_upload(c->toff, toff.data(), toff.size(), st))) return rc;
-  if ((rc = dev_upload(c->tsongs, tsongs.data(), tsongs.size(), st))) return rc;
-  if (!fused && n_chunks > 1) {
-    // Chunk boundaries of every listener list (sorted by train user), built on
-    // the device from the uploaded transpose: the chunked stage 1 reads its
-    // sub-list bounds instead of searching (n_s x (n_chunks + 1) ints).
-    const int nc1 = n_chunks + 1;
-    const size_t n_sb = (size_t)n_s * nc1;
-    if ((rc = dev_alloc(c->sbound, n_sb))) return rc;
-    const int grid = (int)std::min<size_t>(8192, (n_sb + 255) / 256);
-    hipLaunchKernelGGL(k_sbound, dim3(grid), dim3(256), 0, st, c->trs_off.p, c->trs_users.p, n_s, nc1, chunk,
-                       c->sbound.p);
-    MR_HIP(hipGetLastError());
-  }
-  if (fused) {  // n_tr <= 4096 and bs <= 65536: both halves fit 16 bits
-    std::vector<uint32_t> tpack(tsongs.size(), 0u);
-    for (size_t t = 0; t < (size_t)n_tiles; ++t)
-      for (int v = 0; v < n_tr; ++v)
-        for (int32_t i = toff[t * n_tr + v]; i < toff[t * n_tr + v + 1]; ++i)
-          tpack[i] = ((uint32_t)v << 16) | tsongs[i];
-    if ((rc = dev_upload(c->tpack, tpack.data(), tpack.size(), st))) return rc;
-    // The songsToUsersMap lookup (MR:232) of every test-visible song, resolved
-    // once: its listener range in trs_users and its ibm weight.
-    const size_t nte = (size_t)d->te_off[n_te];
-    std::vector<int2> rng(std::max<size_t>(1, nte));
-    std::vector<long long> tq(std::max<size_t>(1, nte));
-    for (size_t i = 0; i < nte; ++i) {
-      const int s2 = d->te_songs[i];
-      rng[i] = make_int2((int)trs_off[s2], (int)(trs_off[s2 + 1] - trs_off[s2]));
-      tq[i] = q_song[s2];
-    }
-    if ((rc = dev_upload(c->te_rng, rng.data(), rng.size(), st))) return rc;
-    if ((rc = dev_upload(c->te_q, tq.data(), tq.size(), st))) return rc;
-    // Stage 1's walk schedule: per test user, its (song, listener) entries in
-    // song order as (trs_users index, slot of the song in T(u)) — the segment
-    // each flattened entry falls in, which the kernel otherwise finds per step
-    // by a prefix scan and a binary search. Index metadata like te_rng (it
-    // names positions, not listener ids or weights); skipped past 2^26 entries.
-    std::vector<long long> h_sched_off((size_t)n_te + 1, 0);
-    for (int u = 0; u < n_te; ++u) {
-      long long n = 0;
-      for (long long i = d->te_off[u]; i < d->te_off[u + 1]; ++i) n += rng[(size_t)i].y;
-      h_sched_off[(size_t)u + 1] = h_sched_off[(size_t)u] + n;
-    }
-    const long long n_sched = h_sched_off[(size_t)n_te];
-    if (fused_sched_opt() && n_sched <= (1ll << 26)) {
-      std::vector<uint2> sched(std::max<long long>(1, n_sched));
-      size_t o = 0;
-      for (int u = 0; u < n_te; ++u)
-        for (long long i = d->te_off[u]; i < d->te_off[u + 1]; ++i)
-          for (int e = 0; e < rng[(size_t)i].y; ++e)
-            sched[o++] = make_uint2((unsigned)(rng[(size_t)i].x + e), (unsigned)(i - d->te_off[u]));
-      if ((rc = dev_upload(c->te_sched, sched.data(), sched.size(), st))) return rc;
-      if ((rc = dev_upload(c->sched_off, h_sched_off.data(), h_sched_off.size(), st))) return rc;
-    }
-  }  // (separate / wide shapes: neighbour lists allocated by the first two-hop run, ensure_nbr)
-  if (route == 2) {
-    const size_t nr = row_song.size();
-    if ((rc = dev_upload(c->row_song, row_song.data(), nr, st))) return rc;
-    if ((rc = dev_upload(c->te_row, te_row.data(), te_row.size(), st))) return rc;
-    if ((rc = dev_upload(c->row_base, reinterpret_cast<const long long*>(row_base.data()), nr + 1, st))) return rc;
-    if ((rc = dev_alloc(c->row_nnz, nr))) return rc;
-    if ((rc = dev_alloc(c->seg_off, nr * n_tiles))) return rc;
-    if ((rc = dev_alloc(c->seg_len, nr * n_tiles))) return rc;
-    if ((rc = dev_alloc(c->pool, (size_t)pool_cap))) return rc;
-    // heavy rows, then light rows with large tables, then the small-table ones
-    std::stable_sort(light_rows.begin(), light_rows.end(), [&](int32_t x, int32_t y) {
-      return light_tier(row_slots[x] & kLightSlotsMask, n_tiles) < light_tier(row_slots[y] & kLightSlotsMask, n_tiles);
-    });
-    std::vector<int32_t> order(heavy_rows);
-    order.insert(order.end(), light_rows.begin(), light_rows.end());
-    if ((rc = dev_upload(c->rows_order, order.data(), order.size(), st))) return rc;
-    int64_t n_lrec = 0;   // k_cooc_group's records: the u16 heavy rows' listeners
-    int64_t n_llrec = 0;  // k_cooc_light*'s records: the light rows' listeners
-    {
-      std::vector<int4> rd(std::max<size_t>(1, order.size()));
-      for (size_t i = 0; i < order.size(); ++i) {
-        const int32_t r = order[i], s2 = row_song[r];
-        const int cnt = (int)(trs_off[s2 + 1] - trs_off[s2]);
-        int z = (int)trs_off[s2];  // the first listener in trs_users
-        if (grp > 0 && (int)i >= n_heavy32 && i < heavy_rows.size()) {  // the first record in lrec
-          z = (int)n_lrec;
-          n_lrec += cnt;
-        } else if (i >= heavy_rows.size()) {  // a light row: its first range record in llrec
-          z = (int)n_llrec;
-          n_llrec += cnt;
-        }
-        rd[i] = make_int4(r, row_slots[r], z, cnt);
-      }
-      if ((rc = dev_upload(c->rdesc, rd.data(), rd.size(), st))) return rc;
-      MR_HIP(hipStreamSynchronize(st));
-    }
-    if ((rc = dev_upload(c->row_slots, row_slots.data(), row_slots.size(), st))) return rc;
-    if (!light_rows.empty() || grp > 0) {
-      // the shard's train rows, shard-local song ids (k_cooc_light's and
-      // k_cooc_group's input)
-      std::vector<int64_t> so((size_t)n_tr + 1, 0);
-      mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
-        for (int64_t v = a; v < b; ++v) {
-          const int32_t* r0 = tr_songs + tr_off[v];
-          const int32_t* r1 = tr_songs + tr_off[v + 1];
-          so[v] = std::lower_bound(r0, r1, hi) - std::lower_bound(r0, r1, lo);
-        }
-      });
-      so[n_tr] = mr_par::exclusive_scan(so.data(), (int64_t)n_tr);
-      // + 4 zero entries: rows_walk's 16-B chunk loads never leave the buffer
-      mr_par::buffer<uint32_t> ss((size_t)so[n_tr] + 4);
-      std::fill(ss.begin() + so[n_tr], ss.end(), 0u);
-      mr_par::parallel_for(n_tr, [&](int64_t a, int64_t b, int) {
-        for (int64_t v = a; v < b; ++v) {
-          const int32_t* r0 = std::lower_bound(tr_songs + tr_off[v], tr_songs + tr_off[v + 1], lo);
-          for (int64_t i = 0; i < so[v + 1] - so[v]; ++i) ss[so[v] + i] = (uint32_t)(r0[i] - lo);
-        }
-      });
-      if ((rc = dev_upload(c->sr_off, reinterpret_cast<const long long*>(so.data()), so.size(), st))) return rc;
-      if ((rc = dev_upload(c->sr_songs, ss.data(), ss.size(), st))) return rc;
-      if (!light_rows.empty()) {  // the light rows' listener ranges
-        if ((rc = dev_alloc(c->llrec, (size_t)std::max<int64_t>(1, n_llrec)))) return rc;
-        hipLaunchKernelGGL(k_llrec, dim3((unsigned)light_rows.size()), dim3(256), 0, st,
-                           c->rdesc.p + heavy_rows.size(), c->row_song.p, c->trs_off.p, c->trs_users.p, c->sr_off.p,
-                           c->llrec.p);
-        MR_HIP(hipGetLastError());
-      }
-      if (grp > 0) {  // k_cooc_group's records, on the device: per user (tile starts), then per (row, listener)
-        if ((rc = dev_alloc(c->urec, (size_t)std::max(1, n_tr) * urec_words))) return rc;
-        hipLaunchKernelGGL(k_urec, dim3((std::max(1, n_tr) + 255) / 256), dim3(256), 0, st, c->sr_off.p,
-                           c->sr_songs.p, n_tr, n_tiles, bs, urec_words, c->urec.p);
-        MR_HIP(hipGetLastError());
-        lrec_words = 1;  // base + (n_grp + 1) u16 starts, a power of 2 of words
-        while (2 * (lrec_words - 1) < n_grp + 1) lrec_words <<= 1;
-        if ((rc = dev_alloc(c->lrec, (size_t)std::max<int64_t>(1, n_lrec) * lrec_words))) return rc;
-        const int n16 = (int)heavy_rows.size() - n_heavy32;
-        if (n16 > 0)
-          hipLaunchKernelGGL(k_lrec, dim3(n16), dim3(256), 0, st, c->rdesc.p + n_heavy32, c->row_song.p,
-                             c->trs_off.p, c->trs_users.p, c->urec.p, urec_words, n_tiles, grp, n_grp, lrec_words,
-                             c->lrec.p);
-        MR_HIP(hipGetLastError());
-        MR_HIP(hipStreamSynchronize(st));
-        c->urec.release();  // (lrec holds what the runs need)
-      }
-      MR_HIP(hipStreamSynchronize(st));  // so / ss die here
-    }
-  }
-  if (k > 0) {
-    // wide: per-tile candidates of one launch (a neighbour batch; the
-    // co-listening route launches up to 65528 users at once)
-    const int cand_users = !wide ? n_te : route == 2 ? std::max(batch, std::min(n_te, 65528)) : batch;
-    const size_t nc = (size_t)cand_users * n_tiles * k;
-    if ((rc = dev_alloc(c->cand_key, nc))) return rc;
-    if ((rc = dev_alloc(c->cand_song, nc))) return rc;
-    // keys then songs in ONE record block: the send buffer of the song-shard
-    // exchange (one all-gather of rec bytes per shard, mr_topk_merge_records_async)
-    const size_t nk = (size_t)n_te * k;
-    if ((rc = dev_alloc(c->top_key, (size_t)topk_record_bytes(nk) / 8))) return rc;
-    c->top_song.p = reinterpret_cast<int*>(c->top_key.p + nk);
-    c->top_song.n = nk;
-    c->top_song.own = false;
-    if ((rc = dev_alloc(c->top_score, (size_t)n_te * k))) return rc;
-    // (the in-launch hand-off's per-user counters, one line each: fused / separate shapes only)
-    const size_t n_ctr = wide ? (size_t)n_te : (size_t)n_te * kCounterStride;
-    if ((rc = dev_alloc(c->counter, n_ctr))) return rc;
-    MR_HIP(hipMemsetAsync(c->counter.p, 0, n_ctr * sizeof(unsigned), st));
-  }
-  const size_t esz = c->opt.out_dtype == MR_OUT_F64 ? 8 : 4;
-  if ((rc = dev_alloc(c->dense, c->opt.dense ? (size_t)n_te * width * esz : 1))) return rc;
-  if ((rc = dev_alloc(c->flag, 1))) return rc;
-
-  c->fused = fused;
-  c->shape = shape;
-  c->ibm_route = route;
-  c->cooc_nt = cooc_nt_opt();
-  {  // the candidate-only tile top-k (wide_cand_topk): top-k-only wide runs
-    const char* e = std::getenv("MR_WIDE_CAND");
-    const int nt = route == 2 ? c->cooc_nt : kWideThreads;  // the scoring kernel's threads
-    c->cand_on = wide && !c->opt.dense && k >= 1 && k <= nt / 16 && !c->opt.topk_lists && bs <= kCandE * nt &&
-                 !(e && e[0] == '0');
-  }
-  c->wide_lds = wide ? (size_t)wide_lds<kWideThreads>(bs, k, n_chunks).total : 0;
-  pick_kernels<MR_UBM>(c);
-  pick_kernels<MR_IBM>(c);
-  c->score_lds = wide ? c->wide_lds
-                      : (size_t)score_lds(bs, fused ? n_tr : 0, k, n_tiles, fused ? 0 : n_chunks).total;
-  if (c->score_lds > 160 * 1024)
-    return fail(MR_E_INVALID, "scoring kernel needs %zu B of LDS (> 160 KiB): lower block_songs or topk",
-                c->score_lds);
-  c->nbr_lds = (size_t)align16(chunk * 8) + kThreads * 16 + (kThreads + 4 + kWaves) * 4;
-  for (int m = 0; m < 2; ++m) {
-    MR_HIP(hipFuncSetAttribute((const void*)c->score_kernel[m], hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)c->score_lds));
-    MR_HIP(hipFuncSetAttribute((const void*)c->nbr_kernel[m], hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)c->nbr_lds));
-  }
-  if (route == 2) {
-    c->n_rows = (int)row_song.size();
-    c->pool_cap = pool_cap;
-    // the score kernel's row descriptors (40 B each: sparse + dense views) in its top-k scratch
-    const WideLds<kWideThreads> WL = c->cooc_nt == 512 ? wide_lds<512>(bs, k, n_chunks).as_wide()
-                                                       : wide_lds<kWideThreads>(bs, k, n_chunks);
-    c->cooc_score_lds = (size_t)WL.total;
-    // (<= 255 per pass: the scoring packs a pass's entry and dense-row prefix sums in one int)
-    c->nseg = std::min(std::min(c->cooc_nt, (WL.total - WL.wk - 8) / 40), 255);
-    if (c->nseg < 16) return fail(MR_E_INVALID, "co-listening route: no LDS for row descriptors");
-    c->cooc_lds = (size_t)cooc_build_lds<false>(bs);
-    c->n_heavy = (int)heavy_rows.size();
-    c->build_reads = 0;
-    for (int64_t x : row_reads) c->build_reads += x;
-    c->row_users.assign(row_song.size(), 0);
-    for (size_t i = 0; i < (size_t)d->te_off[n_te]; ++i)
-      if (te_row[i] >= 0) c->row_users[te_row[i]]++;
-    c->row_reads = row_reads;
-    c->row_listeners.resize(row_song.size());
-    for (size_t r = 0; r < row_song.size(); ++r) c->row_listeners[r] = col_tr[row_song[r]];
-    c->row_light.assign(row_song.size(), 0);
-    for (int32_t r : light_rows) c->row_light[r] = 1;
-    c->n_heavy32 = n_heavy32;
-    c->n_big16 = n_big16;
-    c->grp = grp;
-    c->n_grp = n_grp;
-    c->urec_words = urec_words;
-    c->lrec_words = lrec_words;
-    c->group_nt = cooc_group_nt_opt();
-    if (grp > 0)
-      MR_HIP(hipFuncSetAttribute(c->group_nt == 512 ? (const void*)k_cooc_group<512> : (const void*)k_cooc_group<1024>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, cooc_group_lds(bs, grp)));
-    c->tcap16 = tcap16;
-    c->tcap32 = tcap32;
-    c->dense_div = dense_div;
-    c->force32 = cooc_dense32_opt();
-    c->sat = cooc_sat_opt();
-    c->n_light = (int)light_rows.size();
-    for (int& x : c->n_light_tier) x = 0;
-    for (int32_t r : light_rows) c->n_light_tier[light_tier(row_slots[r] & kLightSlotsMask, n_tiles)]++;
-    for (int t = 0; t < kLightTiers; ++t)
-      if (int rc2 = light_tier_call(t, nullptr, 0, nullptr, CoocParams{})) return rc2;
-    MR_HIP(hipFuncSetAttribute((const void*)c->cooc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)c->cooc_score_lds));
-    MR_HIP(hipFuncSetAttribute((const void*)k_cooc_build<MR_COOC_NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)c->cooc_lds));
-    MR_HIP(hipFuncSetAttribute((const void*)k_cooc_build<MR_COOC_NT16, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               cooc_build_lds<true>(bs)));
-  }
-  if (wide && k > 0) {
-    c->merge_lds = (size_t)merge_lds_bytes(k);
-    MR_HIP(hipFuncSetAttribute((const void*)k_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)c->merge_lds));
-  }
+  // device side
+  if ((rc = upload_base(c, d, ti, lp, scales, tiles))) return rc;
+  if (lp.fused() && (rc = upload_fused(c, d, ti, lp, scales, tiles))) return rc;
+  if (plan.route == 2 && (rc = upload_cooc(c, plan, ti, lp, n_tr))) return rc;
+  if ((rc = alloc_outputs(c, lp, plan.route, n_te))) return rc;
+  c->fused = lp.fused();
+  c->shape = lp.shape;
+  c->cooc = std::move(plan);
+  if ((rc = setup_kernels(c, lp, n_tr))) return rc;
 #ifdef MR_STAMPS
   // scoring workgroups' slots, then (co-listening route) 8 per k_cooc_build workgroup
-  const size_t stamp_users = (size_t)std::max(batch, route == 2 ? std::min(n_te, 65528) : 0) + 8;
+  const size_t stamp_users = (size_t)std::max(lp.batch, c->cooc.route == 2 ? std::min(n_te, 65528) : 0) + 8;
   // scoring workgroups, then 8 per build workgroup (per (row, tile) bound + slack for the
   // group grid's padding), then 8 per light row
-  const size_t build_wgs = (size_t)heavy_rows.size() * n_tiles + 64 * (size_t)std::max(1, n_tiles);
-  const size_t n_stamps = (size_t)n_tiles * stamp_users * kStampSlots + build_wgs * 8 + light_rows.size() * 8;
-  if ((rc = dev_alloc(c->stamps, n_stamps))) return rc;
-  MR_HIP(hipMemsetAsync(c->stamps.p, 0, n_stamps * 8, st));
-  c->bstamp_off = (size_t)n_tiles * stamp_users * kStampSlots;
+  const size_t build_wgs = (size_t)c->cooc.n_heavy() * lp.n_tiles + 64 * (size_t)std::max(1, lp.n_tiles);
+  c->bstamp_off = (size_t)lp.n_tiles * stamp_users * kStampSlots;
   c->lstamp_off = c->bstamp_off + build_wgs * 8;
+  const size_t n_stamps = c->lstamp_off + (size_t)c->cooc.n_light() * 8;
+  if ((rc = dev_alloc(c->stamps, n_stamps))) return rc;
+  MR_HIP(hipMemsetAsync(c->stamps.p, 0, n_stamps * 8, c->stream));
 #endif
-  MR_HIP(hipStreamSynchronize(st));  // host vectors die at return
+  MR_HIP(hipStreamSynchronize(c->stream));  // host vectors die at return
   trace("upload");
 
   c->n_tr = n_tr; c->n_te = n_te; c->n_s = n_s;
-  c->song_lo = lo; c->song_hi = hi; c->width = width;
-  c->block_songs = bs; c->n_tiles = n_tiles;
-  c->cap = cap; c->batch = batch;
-  c->chunk = chunk; c->n_chunks = n_chunks;
+  c->song_lo = lp.lo; c->song_hi = lp.hi; c->width = lp.width;
+  c->block_songs = lp.block_songs; c->n_tiles = lp.n_tiles;
+  c->cap = lp.cap; c->batch = lp.batch;
+  c->chunk = lp.chunk; c->n_chunks = lp.n_chunks;
   c->loaded = true;
   c->ran = false;
   return MR_OK;
@@ -5133,9 +5298,9 @@ int mr_load(mr_ctx* c, const mr_dataset* d) {
 int mr_route_info(const mr_ctx* c, int32_t* route, int32_t* n_rows, int64_t* pool_entries) {
   if (!c) return fail(MR_E_INVALID, "null context");
   if (!c->loaded) return fail(MR_E_STATE, "mr_route_info before mr_load");
-  if (route) *route = c->ibm_route;
-  if (n_rows) *n_rows = c->n_rows;
-  if (pool_entries) *pool_entries = c->pool_cap;
+  if (route) *route = c->cooc.route;
+  if (n_rows) *n_rows = c->cooc.n_rows();
+  if (pool_entries) *pool_entries = c->cooc.pool_cap;
   return MR_OK;
 }
 
@@ -5148,30 +5313,31 @@ int mr_topk_mode(const mr_ctx* c, int32_t* candidate_only) {
 
 int mr_cooc_stats(mr_ctx* c, int64_t* index_nnz, int64_t* consumed, int64_t* build_reads) {
   if (!c) return fail(MR_E_INVALID, "null context");
-  if (!c->loaded || c->ibm_route != 2) return fail(MR_E_STATE, "mr_cooc_stats needs a context on ibm_route 2");
+  if (!c->loaded || c->cooc.route != 2) return fail(MR_E_STATE, "mr_cooc_stats needs a context on ibm_route 2");
   if (!c->cooc_ran) return fail(MR_E_STATE, "mr_cooc_stats before an ibm run");
   MR_HIP(hipSetDevice(c->opt.device));
-  std::vector<unsigned> nnz((size_t)std::max(1, c->n_rows), 0u);
-  if (c->n_rows > 0)
-    MR_HIP(hipMemcpyAsync(nnz.data(), c->row_nnz.p, (size_t)c->n_rows * 4, hipMemcpyDeviceToHost, c->stream));
+  std::vector<unsigned> nnz((size_t)std::max(1, c->cooc.n_rows()), 0u);
+  if (c->cooc.n_rows() > 0)
+    MR_HIP(hipMemcpyAsync(nnz.data(), c->row_nnz.p, (size_t)c->cooc.n_rows() * 4, hipMemcpyDeviceToHost, c->stream));
   MR_HIP(hipStreamSynchronize(c->stream));
   int64_t tot = 0, use = 0;
-  for (int r = 0; r < c->n_rows; ++r) {
+  for (int r = 0; r < c->cooc.n_rows(); ++r) {
     tot += nnz[r];
-    use += (int64_t)nnz[r] * c->row_users[r];
+    use += (int64_t)nnz[r] * c->cooc.row_users[r];
   }
   if (index_nnz) *index_nnz = tot;
   if (consumed) *consumed = use;
-  if (build_reads) *build_reads = c->build_reads;
+  if (build_reads) *build_reads = c->cooc.build_reads;
   return MR_OK;
 }
 
 int mr_cooc_bytes(mr_ctx* c, mr_cooc_bytes_t* out) {
   if (!c || !out) return fail(MR_E_INVALID, "null argument");
-  if (!c->loaded || c->ibm_route != 2) return fail(MR_E_STATE, "mr_cooc_bytes needs a context on ibm_route 2");
+  if (!c->loaded || c->cooc.route != 2) return fail(MR_E_STATE, "mr_cooc_bytes needs a context on ibm_route 2");
   if (!c->cooc_ran) return fail(MR_E_STATE, "mr_cooc_bytes before an ibm run");
   MR_HIP(hipSetDevice(c->opt.device));
-  const int nr = c->n_rows, nt = c->n_tiles;
+  const CoocPlan& p = c->cooc;
+  const int nr = p.n_rows(), nt = c->n_tiles;
   std::vector<int32_t> len((size_t)std::max(1, nr) * nt, 0);
   if (nr > 0)
     MR_HIP(hipMemcpyAsync(len.data(), c->seg_len.p, (size_t)nr * nt * 4, hipMemcpyDeviceToHost, c->stream));
@@ -5191,24 +5357,24 @@ int mr_cooc_bytes(mr_ctx* c, mr_cooc_bytes_t* out) {
     }
     b.index_sparse_entries += sp;
     b.index_dense_songs += ds;
-    b.consumed_sparse_entries += sp * c->row_users[r];
-    b.consumed_dense_songs += ds * c->row_users[r];
-    if (c->row_light[r]) {
+    b.consumed_sparse_entries += sp * p.row_users[r];
+    b.consumed_dense_songs += ds * p.row_users[r];
+    if (p.row_light[r]) {
       b.light_rows++;
-      b.light_reads += c->row_reads[r];
+      b.light_reads += p.row_reads[r];
       b.light_index_bytes += seg;
     } else {
       b.heavy_rows++;
-      b.heavy_reads += c->row_reads[r];
+      b.heavy_reads += p.row_reads[r];
       b.heavy_index_bytes += seg;
       // listener walks: one per tile (k_cooc_build), one per tile group (k_cooc_group: u16 rows)
-      const bool u32row = c->force32 || c->row_listeners[r] >= 65536;
-      b.heavy_visits += (int64_t)c->row_listeners[r] * (c->grp > 0 && !u32row ? c->n_grp : nt);
+      const bool u32row = is_u32_row(c->cooc, p.row_listeners[r]);
+      b.heavy_visits += (int64_t)p.row_listeners[r] * (p.grp > 0 && !u32row ? p.n_grp : nt);
     }
-    b.consumed_bytes += seg * c->row_users[r];
+    b.consumed_bytes += seg * p.row_users[r];
   }
-  b.group_tiles = c->grp;
-  b.n_groups = c->grp > 0 ? c->n_grp : nt;
+  b.group_tiles = p.grp;
+  b.n_groups = p.grp > 0 ? p.n_grp : nt;
   *out = b;
   return MR_OK;
 }
@@ -5290,6 +5456,7 @@ int flush_timing(mr_ctx* c) {
 // launches of <= 65528 users) and the per-user merge of the tile lists.
 int run_cooc(mr_ctx* c) {
   hipStream_t st = c->stream;
+  const CoocPlan& p = c->cooc;
   const bool timed = c->opt.time_kernels != 0;
   const int k = c->opt.topk;
   hipEvent_t* ev = nullptr;
@@ -5303,43 +5470,43 @@ int run_cooc(mr_ctx* c) {
     c->ring_used++;
     MR_HIP(hipEventRecord(ev[0], st));
   }
-  if (c->n_rows > 0) {
-    MR_HIP(hipMemsetAsync(c->row_nnz.p, 0, (size_t)c->n_rows * sizeof(unsigned), st));
-    const bool side = c->side[0] && c->n_light > 0 && cooc_side_opt();
+  if (p.n_rows() > 0) {
+    MR_HIP(hipMemsetAsync(c->row_nnz.p, 0, (size_t)p.n_rows() * sizeof(unsigned), st));
+    const bool side = c->side[0] && p.n_light() > 0 && cooc_side_opt();
     if (side) {
       MR_HIP(hipEventRecord(c->side_fork, st));
       for (int i = 0; i < 2; ++i) MR_HIP(hipStreamWaitEvent(c->side[i], c->side_fork, 0));
     }
-    CoocParams cp{c->n_tr, c->n_rows, c->n_tiles, c->block_songs, c->song_lo, c->song_hi, c->toff.p, c->tsongs.p,
+    CoocParams cp{c->n_tr, p.n_rows(), c->n_tiles, c->block_songs, c->song_lo, c->song_hi, c->toff.p, c->tsongs.p,
                   c->trs_off.p, c->trs_users.p, c->row_song.p, c->row_base.p, c->pool.p,
                   c->seg_off.p, c->seg_len.p, c->rows_order.p, c->sr_off.p, c->sr_songs.p, c->row_slots.p,
-                  c->dense_div, c->force32, 255u, c->stamps.p ? c->stamps.p + c->bstamp_off : nullptr,
+                  p.dense_div, p.force32, 255u, c->stamps.p ? c->stamps.p + c->bstamp_off : nullptr,
                   c->row_nnz.p};
-    cp.sat = c->sat;
+    cp.sat = p.sat;
     // heavy rows: >= 65536 listeners with u32 counters, then the rest with u16 pairs
-    const int n32 = c->n_heavy32, n16 = c->n_heavy - c->n_heavy32;
+    const int n32 = p.n_heavy32, n16 = p.n_heavy() - p.n_heavy32;
     if (n32 > 0) {  // all big: one workgroup per (row, tile)
       CoocParams hp = cp;
       hp.n_big = n32;
-      hp.tcap = c->tcap32;
+      hp.tcap = p.tcap32;
       hipLaunchKernelGGL((k_cooc_build<MR_COOC_NT, false>), dim3(n32 * c->n_tiles), dim3(MR_COOC_NT), c->cooc_lds, st,
                          hp);
       MR_HIP(hipGetLastError());
     }
-    if (n16 > 0 && c->grp > 0) {  // by tile groups: big rows per (row, group), the others per row
+    if (n16 > 0 && p.grp > 0) {  // by tile groups: big rows per (row, group), the others per row
       CoocParams hp = cp;
       hp.rows = c->rows_order.p + n32;
-      hp.n_big = c->n_big16;
-      hp.tcap = c->tcap16;
+      hp.n_big = p.n_big16;
+      hp.tcap = p.tcap16;
       hp.lrec = c->lrec.p;
-      hp.lrec_words = c->lrec_words;
-      hp.grp = c->grp;
-      hp.n_grp = c->n_grp;
+      hp.lrec_words = p.lrec_words;
+      hp.grp = p.grp;
+      hp.n_grp = p.n_grp;
       hp.rdesc = c->rdesc.p + n32;
       if (hp.stamps) hp.stamps += (size_t)n32 * c->n_tiles * 8;
-      const int nblk = (c->n_big16 + 7) / 8 * 8 * c->n_grp + (n16 - c->n_big16);
-      const size_t glds = (size_t)cooc_group_lds(c->block_songs, c->grp);
-      if (c->group_nt == 512)
+      const int nblk = (p.n_big16 + 7) / 8 * 8 * p.n_grp + (n16 - p.n_big16);
+      const size_t glds = (size_t)cooc_group_lds(c->block_songs, p.grp);
+      if (p.group_nt == 512)
         hipLaunchKernelGGL(k_cooc_group<512>, dim3(nblk), dim3(512), glds, st, hp);
       else
         hipLaunchKernelGGL(k_cooc_group<1024>, dim3(nblk), dim3(1024), glds, st, hp);
@@ -5347,10 +5514,10 @@ int run_cooc(mr_ctx* c) {
     } else if (n16 > 0) {
       CoocParams hp = cp;
       hp.rows = c->rows_order.p + n32;
-      hp.n_big = c->n_big16;
-      hp.tcap = c->tcap16;
+      hp.n_big = p.n_big16;
+      hp.tcap = p.tcap16;
       if (hp.stamps) hp.stamps += (size_t)n32 * c->n_tiles * 8;
-      hipLaunchKernelGGL((k_cooc_build<MR_COOC_NT16, true>), dim3(c->n_big16 * c->n_tiles + n16 - c->n_big16),
+      hipLaunchKernelGGL((k_cooc_build<MR_COOC_NT16, true>), dim3(p.n_big16 * c->n_tiles + n16 - p.n_big16),
                          dim3(MR_COOC_NT16),
                          (size_t)cooc_build_lds<true>(c->block_songs), st, hp);
       MR_HIP(hipGetLastError());
@@ -5358,17 +5525,17 @@ int run_cooc(mr_ctx* c) {
     // light rows on two side streams (tiers 0-1 and 2-3), concurrent with
     // the heavy rows on the context stream: the launches' tails overlap
     // (8 x 1 shards: most rows are light, 4 short launches per step)
-    int lr = c->n_heavy;
+    int lr = p.n_heavy();
     for (int t = 0; t < kLightTiers; ++t) {
-      if (c->n_light_tier[t] == 0) continue;
+      if (p.n_light_tier[t] == 0) continue;
       CoocParams lp = cp;
       lp.rows = c->rows_order.p + lr;
       lp.rdesc = c->rdesc.p + lr;
       lp.llrec = reinterpret_cast<const unsigned*>(c->llrec.p);
-      lp.lstamps = c->stamps.p ? c->stamps.p + c->lstamp_off + (size_t)(lr - c->n_heavy) * 8 : nullptr;
+      lp.lstamps = c->stamps.p ? c->stamps.p + c->lstamp_off + (size_t)(lr - p.n_heavy()) * 8 : nullptr;
       hipStream_t ls = side ? c->side[t < 2 ? 0 : 1] : st;
-      if (int rc2 = light_tier_call(t, ls, c->n_light_tier[t], &lp, lp)) return rc2;
-      lr += c->n_light_tier[t];
+      if (int rc2 = light_tier_call(t, ls, p.n_light_tier[t], &lp, lp)) return rc2;
+      lr += p.n_light_tier[t];
     }
     if (side)
       for (int i = 0; i < 2; ++i) {
@@ -5391,7 +5558,7 @@ int run_cooc(mr_ctx* c) {
     sp.frac_bits = c->opt.frac_bits; sp.topk = k; sp.dense = c->opt.dense;
     sp.te_off = c->te_off.p; sp.te_songs = c->te_songs.p;
     sp.sqrt_c = c->sqrt_c.p; sp.q_song = c->q_song.p;
-    sp.n_rows = c->n_rows; sp.nseg = c->nseg;
+    sp.n_rows = p.n_rows(); sp.nseg = c->nseg;
     sp.te_row = c->te_row.p; sp.seg_off = c->seg_off.p; sp.seg_len = c->seg_len.p; sp.pool = c->pool.p;
     sp.dense_out = c->dense_override ? c->dense_override : (void*)c->dense.p;
     sp.cand_key = c->cand_key.p; sp.cand_song = c->cand_song.p; sp.counter = c->counter.p;
@@ -5400,7 +5567,7 @@ int run_cooc(mr_ctx* c) {
     sp.topk_lists = c->opt.topk_lists;
     if (c->mm_on) { sp.mm_key = c->mm_key.p; sp.mm_n = c->n_te; }
     sp.cand = c->cand_on && !sp.mm_key; sp.rsq_c = c->rsq_c.p;
-    hipLaunchKernelGGL(c->cooc_kernel, dim3(c->n_tiles, (ny + 7) / 8 * 8), dim3(c->cooc_nt), c->cooc_score_lds, st, sp);
+    hipLaunchKernelGGL(c->cooc_kernel, dim3(c->n_tiles, (ny + 7) / 8 * 8), dim3(p.cooc_nt), c->cooc_score_lds, st, sp);
     MR_HIP(hipGetLastError());
     if (k > 0 && c->n_tiles > 1) {
       MergeParams mp{c->n_tiles, k, k, (long long)c->n_tiles * k, (long long)k, (long long)k, c->cand_key.p,
@@ -5429,7 +5596,7 @@ int ensure_nbr(mr_ctx* c) {
 }
 
 int run_model(mr_ctx* c, int model) {
-  if (model == MR_IBM && c->ibm_route == 2) {
+  if (model == MR_IBM && c->cooc.route == 2) {
     c->cooc_ran = true;
     return run_cooc(c);
   }
@@ -5720,7 +5887,7 @@ int mr_graph_capture(mr_ctx* c, int model, int32_t n_steps) {
   if (c->opt.time_kernels) return fail(MR_E_STATE, "graph capture of a context with time_kernels=1");
   MR_HIP(hipSetDevice(c->opt.device));
   MR_HIP(hipStreamSynchronize(c->stream));
-  if (!(model == MR_IBM && c->ibm_route == 2)) {  // no allocation inside the capture
+  if (!(model == MR_IBM && c->cooc.route == 2)) {  // no allocation inside the capture
     if (int rc0 = ensure_nbr(c)) return rc0;
   }
   if (c->graph_exec) { MR_HIP(hipGraphExecDestroy(c->graph_exec)); c->graph_exec = nullptr; }
