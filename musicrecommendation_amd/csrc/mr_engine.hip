@@ -557,12 +557,14 @@ __device__ __forceinline__ void block_topk_wide(int n, int k, Get get, long long
 }
 
 // Block top-k by threshold, for large n. Candidates are totally ordered by
-// (key desc, song asc) (cand_before), so the k-th best of the NT/16 row bests
-// (16-lane groups) is a lower bound tau on the k-th best entry (those k are k
+// (key desc, song asc) (cand_before), so the k-th best of the NG row bests
+// (groups of NT / NG threads; NG = NT / 16 by default) is a lower bound tau on the k-th best entry (those k are k
 // distinct entries): every top-k entry comes before or equal to tau. A second
 // pass collects those entries (about k of them, ties included: the bound is a
 // (key, song) pair) into ck/cs (cap <= 256 slots), and every candidate's rank
-// among them (pairwise comparisons spread over the block) is its output slot.
+// among them (pairwise comparisons spread over the block, about kRankQ<NT>
+// per thread at most; more survivors than that go to one wave's select:
+// rank_survivors) is its output slot.
 // Each thread passes the best of its own keys (mk, ms) — get(i) for
 // i = tid + NT j, which the caller has usually just produced. Scratch gm:
 // topk_scratch_bytes(NT). Returns false, uniformly, when the candidates
@@ -1946,9 +1948,16 @@ __device__ __forceinline__ void walk_tile_lists(int tid, int cnt, LoadList&& loa
 // key ≤ 2^-52. The k songs behind tau have exact scores ≥ tau(1 − δ)/(1 + δ),
 // so the k-th best exact score is too, and any song ranked at or above it has
 // a ≥ tau(1 − 2δ − 2ε) > tau(1 − 2^-17). Ties of exact scores have equal
-// approximations (same acc, same c). Returns false, uniformly, when the
-// survivors overflow cap (e.g. fewer than k positive scores: tau = 0); acc
-// is untouched, so the caller then runs the all-songs path.
+// approximations only for the same (acc, c) — every ubm tie, since there
+// a = float(acc). ItemBasedModel scores from different (acc, c) can be the
+// same real number (30/√50 = 18/√18) or within a few 2^-24 of each other
+// (C1²·c2 − C2²·c1 = ±1), with fp64 keys that tie or differ by an ulp while
+// the approximations differ, even in the other direction; the bound above
+// makes no use of a's order, so the 2^-17 margin keeps both songs and the
+// exact ranking decides (tests/topk_cases.py, near_ties). Returns false,
+// uniformly, when the survivors overflow cap (e.g. fewer than k positive
+// scores: tau = 0, or more tied songs at tau than cap); acc is untouched, so
+// the caller then runs the all-songs path.
 #ifndef MR_CAND_EB
 #define MR_CAND_EB 4  // wide_cand_topk: songs per thread whose loads are issued together (5 / 7 slower, 10 spilled)
 #endif
@@ -6122,7 +6131,12 @@ int mr_topk_dense_device(mr_ctx* c, const void* dense_dev, int32_t k) {
   unsigned neg = 0;
   MR_HIP(hipMemcpyAsync(&neg, c->flag.p, sizeof neg, hipMemcpyDeviceToHost, c->stream));
   MR_HIP(hipStreamSynchronize(c->stream));
-  if (neg) return fail(MR_E_INVALID, "dense model has negative scores: top-k keys need scores >= 0");
+  if (neg) {
+    // the kernels have overwritten the lists of the previous run with lists
+    // that skip the negative scores: nothing to read until the next run
+    c->ran = false;
+    return fail(MR_E_INVALID, "dense model has negative scores: top-k keys need scores >= 0");
+  }
   c->ran = true;
   return MR_OK;
 }
