@@ -453,6 +453,48 @@ int mr_sweep_map_device(mr_ctx* ctx, int kind, int32_t n_params, const double* p
                         const int32_t* lab_songs, const int32_t* pos, int32_t n_label_songs, double* maps_out,
                         double* minmax_out, int32_t n_thresholds);
 
+/* ---- full ranked recommendation lists and the truncated mAP@k ----------------
+ * (the Million Song Dataset Challenge's deliverable: 500 songs per user, scored
+ * by mAP truncated at 500.) Independent of the context's topk and of mr_run's
+ * top-k paths.
+ * mr_rank_dense_device: per test user of the context, the K valid entries of
+ *   the row dense[u][0..width) (DEVICE, the context's out_dtype, NaN = no pair)
+ *   with the highest stored value, ordered by (value descending, global song id
+ *   = song_lo + column ascending) — a radix select and an LDS sort, one
+ *   workgroup per user (csrc/mr_rank.hip). The order is total: -0.0 ranks as
+ *   +0.0 (and is returned as +0.0), negative values rank below zero in numeric
+ *   order, denormals are distinct, +-inf are ordinary values; f32 models are
+ *   ranked on the stored f32 value, returned widened to double. songs_dev
+ *   [n_te][K] int32 and scores_dev [n_te][K] double (may be NULL) are
+ *   caller-owned DEVICE buffers; missing slots (fewer than K valid entries)
+ *   hold song -1 and score NaN. The lists are a pure function of the row.
+ *   1 <= K <= MR_RANK_MAX_K. Synchronous on the context stream. Every argument
+ *   is checked before any launch: MR_E_INVALID for a bad K or a NULL dense_dev /
+ *   songs_dev, MR_E_STATE before mr_load.
+ * mr_rank_merge_host: merges n_lists lists per user (HOST, [list][n_te][K],
+ *   global song ids, -1 = empty slot) by the same order into [n_te][K]: the
+ *   lists of the song shards of one model give the one-context lists.
+ * mr_rank_map_host / mr_rank_map_device: the truncated mAP over the first
+ *   k_eval <= K slots of [n_te][K] lists (HOST / DEVICE songs), labels as the
+ *   host CSR of mr_eval_counts_device (a set per user: duplicates count once;
+ *   label-only ids >= n_songs count in n_u = |labels(u)|):
+ *     hit_i = slot i holds a song >= 0 in labels(u); h_i = hits in slots 1..i;
+ *     AP(u) = (left fold over i = 1..k_eval of (hit_i ? (double)h_i / (double)i : 0.0))
+ *             / (double)min(k_eval, n_u), 0 when n_u = 0;
+ *     map = (left fold over u of AP(u)) / n_te, 0.0 when n_te = 0.
+ *   ap_out (HOST [n_te], may be NULL) receives AP(u). On the device the
+ *   membership is a binary search in the user's sorted distinct labels, one lane
+ *   folds in rank order, and the user sum runs on the host: both calls agree
+ *   bit for bit. n_te of the device call is the context's. */
+#define MR_RANK_MAX_K 1024
+int mr_rank_dense_device(mr_ctx* ctx, const void* dense_dev, int32_t K, int32_t* songs_dev, double* scores_dev);
+int mr_rank_merge_host(int32_t n_lists, int32_t n_te, int32_t K, const int32_t* songs_in, const double* scores_in,
+                       int32_t* songs_out, double* scores_out);
+int mr_rank_map_device(mr_ctx* ctx, const int32_t* songs_dev, int32_t K, int32_t k_eval, const int64_t* lab_off,
+                       const int32_t* lab_songs, double* ap_out, double* map_out);
+int mr_rank_map_host(int32_t n_te, const int32_t* songs, int32_t K, int32_t k_eval, const int64_t* lab_off,
+                     const int32_t* lab_songs, double* ap_out, double* map_out);
+
 /* Kernel timing of mr_run calls made with opt.time_kernels = 1: per kernel
  * (0 = separate stage-1 kernel — neighbour lists —, 1 = the
  * scoring kernels — stage 2, fused stage 1, the in-launch top-k merge, the wide

@@ -119,6 +119,7 @@ MR_COMB_LINEAR = 0
 MR_COMB_AGGREGATION = 1
 MR_COMB_STOCHASTIC = 2
 MR_SWEEP_MAX_PARAMS = 64
+MR_RANK_MAX_K = 1024
 
 
 class EngineError(RuntimeError):
@@ -190,6 +191,12 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_int32]),
     "mr_sweep_map_device": (c_int, [c_void_p, c_int, c_int32, c_void_p, ctypes.c_uint64, c_int64, c_int64, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32]),
+    "mr_rank_dense_device": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "mr_rank_merge_host": (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mr_rank_map_device": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                   POINTER(c_double)]),
+    "mr_rank_map_host": (c_int, [c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                 POINTER(c_double)]),
     "mr_last_error": (c_char_p, []),
     "mr_corpus_from_tsv": (c_int, [c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
     "mr_corpus_dataset": (c_int, [c_void_p, POINTER(MrDataset)]),

@@ -3,7 +3,7 @@ MN:8-123, src/main/scala/distributed.scala DS:55-602) on the MI355X engine.
 
     python -m musicrecommendation_amd.driver TRAIN_N TEST_N [--resources DIR]
         [--devices 0,1,...] [--song-shards G_s] [--user-blocks G_u] [--distributed] [--quiet]
-        [--sweep KIND:LO:HI:N ...]
+        [--sweep KIND:LO:HI:N ...] [--recommend K[:PATH]]
 
 Same flow and output as main.scala: load train_{N}_{M}.txt, test_{N}_{M}.txt,
 test_labels_{N}_{M}.txt (MN:21-23), build the recommender (untimed, MN:27),
@@ -30,6 +30,13 @@ values from LO to HI over the same two device models, one line per value and
 the best one — the experiment the reference's README leaves open, where the
 driver and main.scala hard-code 0.5 (DeviceEnsemble.sweep: no combined model
 is materialised).
+
+--recommend K[:PATH] (K <= 1024) ranks each of the five models after the flow:
+per test user the K best songs by (score desc, song asc), selected on the
+device (DeviceEnsemble.rank), and prints each model's mAP truncated at K — the
+Million Song Dataset Challenge's metric at K = 500 — beside the threshold
+mAPs. With PATH the linear-combination model's lists are written there, one
+"user<TAB>song<TAB>score" line per recommendation in (user, rank) order.
 """
 from __future__ import annotations
 
@@ -83,6 +90,29 @@ def parse_sweep(spec: str) -> Tuple[str, float, float, int]:
     return kind, lo, hi, n
 
 
+def parse_recommend(spec) -> Tuple[int, Optional[str]]:
+    """--recommend K[:PATH] (or an int K, or (K, PATH)) -> (K, path or None);
+    ValueError on a bad spec."""
+    from ._lib import MR_RANK_MAX_K
+
+    if isinstance(spec, (tuple, list)):
+        k, path = spec[0], (spec[1] if len(spec) > 1 else None)
+    elif isinstance(spec, str):
+        head, sep, tail = spec.partition(":")
+        k, path = head, (tail if sep else None)
+        if sep and not tail:
+            raise ValueError(f"--recommend {spec!r}: empty PATH")
+    else:
+        k, path = spec, None
+    try:
+        k = int(k)
+    except (TypeError, ValueError):
+        raise ValueError(f"--recommend {spec!r}: expected K[:PATH], K an integer") from None
+    if not 1 <= k <= MR_RANK_MAX_K:
+        raise ValueError(f"--recommend {spec!r}: K must be in [1, {MR_RANK_MAX_K}]")
+    return k, (os.fspath(path) if path is not None else None)
+
+
 def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
     """N evenly spaced values LO + i*(HI-LO)/(N-1) (N = 1: LO alone)."""
     return [lo + i * (hi - lo) / (n - 1) for i in range(n)] if n > 1 else [lo]
@@ -90,7 +120,7 @@ def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
 
 def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[int]] = None,
         song_shards: Optional[int] = None, user_blocks: int = 1, verbose: bool = True, seed: int = 1,
-        distributed: bool = False, sweeps: Optional[Sequence[str]] = None) -> dict:
+        distributed: bool = False, sweeps: Optional[Sequence[str]] = None, recommend=None) -> dict:
     import numpy as np
 
     from .dataset import Dataset
@@ -98,6 +128,7 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
     from .ensemble import DeviceEnsemble, best
 
     specs = [parse_sweep(s) if isinstance(s, str) else tuple(s) for s in (sweeps or [])]  # before any work
+    rec = parse_recommend(recommend) if recommend is not None else None
 
     n_thr = 11 if distributed else 10  # DS:395 vs MR:590
     if song_shards is None:  # one song shard per listed GPU and user block (DS:477-479's song partition)
@@ -143,6 +174,23 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
         maps[name] = timed(lambda: ens.threshold_map(t, n_thresholds=n_thr), f"{name} model mAP", verbose)  # MN:101-110
     for name, v in maps.items():
         print(f"{name} model mAP: {round_at(10, v)}", flush=True)                              # MN:112-121
+    ranked = {}
+    if rec is not None:
+        from . import modelio
+
+        rk, rpath = rec
+        for name, t in (("user-based", ubm), ("item-based", ibm), ("linear-combination", lcm), ("aggregation", am),
+                        ("stochastic-combination", scm)):
+            lists = timed(lambda: ens.rank(t, rk), f"{name} model top-{rk} lists", verbose)
+            ranked[name] = ens.map_at(lists, rk)
+            if rpath is not None and name == "linear-combination":
+                songs, scores = lists[0].cpu().numpy(), lists[1].cpu().numpy()
+                modelio.write_recommendations(rpath, [
+                    (ds.test_names(u), [(ds.song_names(int(g)), float(x))
+                                        for g, x in zip(songs[u], scores[u]) if g >= 0])
+                    for u in range(ds.n_test)])
+        for name, v in ranked.items():
+            print(f"{name} model mAP@{rk}: {round_at(10, v)}", flush=True)
     swept = []
     for kind, lo, hi, n in specs:
         params = sweep_grid(lo, hi, n)
@@ -158,12 +206,22 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
            "layout": (song_shards, user_blocks)}
     if specs:
         out["sweeps"] = swept
+    if rec is not None:
+        out["mAP@K"] = ranked
+        out["recommend"] = {"K": rec[0], "path": rec[1]}
     return out
 
 
 def _sweep_arg(spec: str) -> Tuple[str, float, float, int]:
     try:
         return parse_sweep(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _recommend_arg(spec: str) -> Tuple[int, Optional[str]]:
+    try:
+        return parse_recommend(spec)
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e)) from None
 
@@ -184,11 +242,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--sweep", action="append", default=[], metavar="KIND:LO:HI:N", type=_sweep_arg,
                     help="after the flow, the mAP of KIND (linear, aggregation, stochastic) at N evenly spaced "
                          "parameter values from LO to HI; repeatable")
+    ap.add_argument("--recommend", default=None, metavar="K[:PATH]", type=_recommend_arg,
+                    help="after the flow, rank the K best songs per test user of each model (K <= 1024), print "
+                         "each model's mAP@K, and write the linear-combination model's lists to PATH")
     a = ap.parse_args(argv)
     devices = [int(x) for x in a.devices.split(",") if x.strip()] if a.devices else None
     train_n = a.train_n if a.train_n is not None else (300 if a.distributed else 100)
     run(train_n, a.test_n, a.resources, devices, a.song_shards, a.user_blocks, verbose=not a.quiet, seed=a.seed,
-        distributed=a.distributed, sweeps=a.sweep)
+        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend)
     return 0
 
 

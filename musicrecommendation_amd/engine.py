@@ -380,6 +380,31 @@ class Engine:
         maps = out[:par.shape[0]].tolist()
         return (maps, mm[:par.shape[0]]) if minmax else maps
 
+    # ---- full ranked lists (mr_rank_*: K up to MR_RANK_MAX_K, any topk) --------
+    def rank_dense(self, dense_ptr: int, K: int, songs_ptr: int, scores_ptr: int = 0) -> None:
+        """The K best (song, score) per test user of a dense device model by
+        (score desc, song asc) into caller-owned device buffers: songs int32
+        [n_test][K], scores float64 [n_test][K] (0: none); empty slots hold
+        -1 / NaN; synchronous (mr_rank_dense_device)."""
+        _lib.check(self._L.mr_rank_dense_device(self._h, ctypes.c_void_p(dense_ptr), int(K),
+                                                ctypes.c_void_p(songs_ptr), ctypes.c_void_p(scores_ptr or None)),
+                   "mr_rank_dense_device")
+
+    def rank_map(self, songs_ptr: int, K: int, k_eval: int, lab_off: np.ndarray,
+                 lab_songs: np.ndarray) -> Tuple[float, np.ndarray]:
+        """(mAP@k_eval, AP per test user) of [n_test][K] device lists, the fold
+        on the device (mr_rank_map_device); bit-equal to rank_map_host."""
+        lab_off = np.ascontiguousarray(lab_off, dtype=np.int64)
+        lab_songs = np.ascontiguousarray(lab_songs, dtype=np.int32)
+        ap = np.empty(max(1, self.n_test), dtype=np.float64)
+        out = ctypes.c_double()
+        _lib.check(self._L.mr_rank_map_device(self._h, ctypes.c_void_p(songs_ptr), int(K), int(k_eval),
+                                              lab_off.ctypes.data_as(ctypes.c_void_p),
+                                              lab_songs.ctypes.data_as(ctypes.c_void_p),
+                                              ap.ctypes.data_as(ctypes.c_void_p), ctypes.byref(out)),
+                   "mr_rank_map_device")
+        return out.value, ap[:self.n_test]
+
     def timing_begin(self) -> None:
         """Open a timing window (one event on the engine stream)."""
         _lib.check(self._L.mr_timing_begin(self._h), "mr_timing_begin")
@@ -419,3 +444,42 @@ def merge_topk_host(songs: np.ndarray, keys: np.ndarray) -> Tuple[np.ndarray, np
                                     os_.ctypes.data_as(ctypes.c_void_p), ok.ctypes.data_as(ctypes.c_void_p),
                                     osc.ctypes.data_as(ctypes.c_void_p)), "mr_topk_merge_host")
     return os_, osc, ok
+
+
+def rank_merge_host(songs: np.ndarray, scores: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Merge [n_lists][n_test][K] ranked lists (global song ids, -1 = empty)
+    into n_test x K by (score desc, song asc): the lists of a model's song
+    shards give the one-context lists (mr_rank_merge_host)."""
+    songs = np.ascontiguousarray(songs, dtype=np.int32)
+    scores = np.ascontiguousarray(scores, dtype=np.float64)
+    if songs.ndim != 3 or scores.shape != songs.shape:
+        raise ValueError("songs and scores: [n_lists][n_test][K] arrays of one shape")
+    g, n_te, k = songs.shape
+    os_ = np.empty((n_te, k), dtype=np.int32)
+    osc = np.empty((n_te, k), dtype=np.float64)
+    _lib.check(_lib.lib().mr_rank_merge_host(g, n_te, k, songs.ctypes.data_as(ctypes.c_void_p),
+                                             scores.ctypes.data_as(ctypes.c_void_p),
+                                             os_.ctypes.data_as(ctypes.c_void_p),
+                                             osc.ctypes.data_as(ctypes.c_void_p)), "mr_rank_merge_host")
+    return os_, osc
+
+
+def rank_map_host(songs: np.ndarray, k_eval: int, lab_off: np.ndarray,
+                  lab_songs: np.ndarray) -> Tuple[float, np.ndarray]:
+    """(mAP@k_eval, AP per user) of n_test x K host lists (mr_rank_map_host)."""
+    songs = np.ascontiguousarray(songs, dtype=np.int32)
+    if songs.ndim != 2:
+        raise ValueError("songs: an n_test x K array")
+    n_te, k = songs.shape
+    lab_off = np.ascontiguousarray(lab_off, dtype=np.int64)
+    lab_songs = np.ascontiguousarray(lab_songs, dtype=np.int32)
+    if lab_off.shape[0] != n_te + 1:
+        raise ValueError("lab_off: n_test + 1 offsets")
+    ap = np.empty(max(1, n_te), dtype=np.float64)
+    out = ctypes.c_double()
+    _lib.check(_lib.lib().mr_rank_map_host(n_te, songs.ctypes.data_as(ctypes.c_void_p), k, int(k_eval),
+                                           lab_off.ctypes.data_as(ctypes.c_void_p),
+                                           lab_songs.ctypes.data_as(ctypes.c_void_p),
+                                           ap.ctypes.data_as(ctypes.c_void_p), ctypes.byref(out)),
+               "mr_rank_map_host")
+    return out.value, ap[:n_te]

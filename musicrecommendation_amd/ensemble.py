@@ -20,6 +20,11 @@ sweep answers what the combinations exist for — which parameter value to use
 (the reference hard-codes 0.5): the mAP of one combination kind at P values,
 the combination formed in registers (mr_sweep_*), no combined model written;
 across ranks the same two all-reduces as threshold_maps.
+
+rank / map_at give what the scores are for: per test user the K <= 1024 best
+songs of any dense model by (score desc, song asc) — a radix select and an LDS
+sort per user (csrc/mr_rank.hip), negative scores included — and the mAP
+truncated at k over such lists, folded on the device in a fixed order.
 """
 from __future__ import annotations
 
@@ -369,3 +374,33 @@ class DeviceEnsemble:
         self._after_torch()
         self.e.topk_dense(t.data_ptr())
         return self.e.topk()
+
+    # ---- full ranked lists (mr_rank_*) -------------------------------------------
+    def rank(self, t, K: int):
+        """The K best (song, score) per test user of a dense device model, by
+        (score desc, global song id asc), as device tensors (songs int32,
+        scores float64), each n_test x K; empty slots hold -1 / NaN. K up to
+        MR_RANK_MAX_K, whatever the engine's topk; negative scores rank too."""
+        import torch
+
+        K = int(K)
+        songs = torch.empty((self.e.n_test, max(K, 1)), dtype=torch.int32, device=self.device)
+        scores = torch.empty((self.e.n_test, max(K, 1)), dtype=torch.float64, device=self.device)
+        self._after_torch()
+        self.e.rank_dense(t.data_ptr(), K, songs.data_ptr(), scores.data_ptr())
+        return songs, scores
+
+    def map_at(self, lists_or_model, k: int, K: Optional[int] = None) -> float:
+        """The challenge's truncated mAP@k (evaluation.map_at_k's definition in
+        mr_rank_map_device's fixed summation order) of ranked lists — an
+        n_test x K int32 device tensor, or rank()'s (songs, scores) pair — or of
+        a dense device model, ranked first at K (default k)."""
+        import torch
+
+        x = lists_or_model[0] if isinstance(lists_or_model, (tuple, list)) else lists_or_model
+        if x.dtype != torch.int32:
+            x = self.rank(x, int(K if K is not None else k))[0]
+        if x.dim() != 2 or x.shape[0] != self.e.n_test or not x.is_contiguous():
+            raise ValueError("lists: a contiguous n_test x K int32 tensor")
+        self._after_torch()
+        return self.e.rank_map(x.data_ptr(), int(x.shape[1]), int(k), self.ds.lab_off, self.ds.lab_songs)[0]

@@ -7,6 +7,9 @@
   + R_8·P_8 + 0 (MR:601-609), mAP = Σ AP / |newSongs| (MR:626).
 * ``map_at_k`` — the build-defined mAP@k over the engine's top-k lists
   (SURVEY.md §8d): AP@k(u) = Σ_{i<=k} P@i·rel(i) / min(k, |labels(u)|).
+* ``rank_lists`` — the numpy restatement of the engine's full ranked lists
+  (mr_rank_dense_device): per user the K best valid entries by (value desc,
+  song id asc).
 Vectorised over the dense n_test x n_songs score matrix (NaN = no pair).
 """
 from __future__ import annotations
@@ -117,3 +120,23 @@ def map_at_k(top_songs: np.ndarray, ds: Dataset, k: int = 10) -> float:
     ap = (hit * (np.cumsum(hit, axis=1) / ranks)).sum(axis=1)
     denom = np.minimum(k, n_lab)
     return float(np.where(denom > 0, ap / np.maximum(denom, 1), 0.0).sum() / n_te)
+
+
+def rank_lists(dense: np.ndarray, K: int, song_lo: int = 0):
+    """(songs int32, scores float64), each n_users x K: per row of a dense model
+    (NaN = no pair) the K valid entries with the highest stored value, ordered
+    by (value desc, song id = song_lo + column asc); -0.0 ranks and is returned
+    as +0.0; missing slots hold -1 / NaN. The numpy twin of
+    mr_rank_dense_device (f32 values widen to float64 exactly)."""
+    d = np.asarray(dense)
+    if d.ndim != 2 or K < 1:
+        raise ValueError("rank_lists: a 2-d model and K >= 1")
+    songs = np.full((d.shape[0], K), -1, dtype=np.int32)
+    scores = np.full((d.shape[0], K), np.nan, dtype=np.float64)
+    for u in range(d.shape[0]):
+        cols = np.nonzero(~np.isnan(d[u]))[0]
+        vals = d[u, cols].astype(np.float64) + 0.0  # -0.0 + 0.0 = +0.0
+        order = np.lexsort((cols, -vals))[:K]       # value desc, then column asc
+        songs[u, :order.size] = cols[order] + song_lo
+        scores[u, :order.size] = vals[order]
+    return songs, scores

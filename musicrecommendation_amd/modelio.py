@@ -6,6 +6,9 @@ engine library's host code (csrc/mr_modelio.cpp):
 * ``read_dense``  — importModelFromFile (MR:505-512) into a dense model over a
   dataset's interned names (NaN where the file has no pair);
 * ``java_double_string`` — Scala's ``s"${x}"`` of a Double.
+* ``write_recommendations`` / ``read_recommendations`` — ranked lists
+  (MusicRecommender.recommend) as ``user\\tsong\\tscore`` lines in (user, rank)
+  order, scores in the same format; a user without a filled slot has no line.
 """
 from __future__ import annotations
 
@@ -72,3 +75,31 @@ def import_model(path: str) -> List[Tuple[str, str, float]]:
             rows.append((parts[0], parts[1], float(parts[2])))
     rows.sort(key=lambda t: (t[0], t[1], -t[2]))
     return rows
+
+
+Recommendations = List[Tuple[str, List[Tuple[str, float]]]]
+
+
+def write_recommendations(path: str, recs: Recommendations) -> None:
+    """Ranked lists ([(user, [(song, score), ...])], MusicRecommender.recommend)
+    as one ``user\\tsong\\tscore`` line per filled slot, in (user, rank) order;
+    scores as java.lang.Double.toString, the shortest digits that round-trip."""
+    with open(path, "w") as f:
+        for user, items in recs:
+            for song, score in items:
+                f.write(f"{user}\t{song}\t{java_double_string(score)}\n")
+
+
+def read_recommendations(path: str) -> Recommendations:
+    """The lists write_recommendations wrote: users in file order, each with
+    its (song, score) lines in rank order (a user's lines are consecutive)."""
+    out: Recommendations = []
+    with open(path) as f:
+        for n, line in enumerate(f, start=1):
+            parts = line.rstrip("\r\n").split("\t")
+            if len(parts) != 3:
+                raise ValueError(f"{path}:{n}: expected 3 tab-separated fields")
+            if not out or out[-1][0] != parts[0]:
+                out.append((parts[0], []))
+            out[-1][1].append((parts[1], float(parts[2])))
+    return out

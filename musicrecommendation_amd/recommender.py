@@ -197,6 +197,44 @@ class MusicRecommender:
         ubm, ibm = ens.model("ubm"), ens.model("ibm")
         return list(zip(params, ens.sweep(kind, ubm, ibm, params, seed=seed)))
 
+    # ---- ranked recommendation lists (DeviceEnsemble.rank / map_at) ----------------
+    def _device_model(self, model):
+        """(ensemble, dense device tensor) of a model given by name ("ubm",
+        "ibm"), as a dense n_test x n_songs array or as a pair list."""
+        import torch
+
+        from .ensemble import DeviceEnsemble
+
+        eng = self.engine()
+        ens = DeviceEnsemble(eng)
+        if isinstance(model, str):
+            return ens, ens.model(model)
+        dense = model if isinstance(model, np.ndarray) else self._from_model(model)
+        if dense.shape != (self.dataset.n_test, self.dataset.n_songs):
+            raise ValueError(f"dense model shape {dense.shape} != ({self.dataset.n_test}, {self.dataset.n_songs})")
+        return ens, torch.from_numpy(np.ascontiguousarray(dense, dtype=eng.dtype)).to(ens.device)
+
+    def recommend(self, model: Union[str, Model, np.ndarray], K: int = 500) -> List[Tuple[str, List[Tuple[str, float]]]]:
+        """Per test user (in user order) the K best unheard songs of a model by
+        (score desc, song asc), by name: [(user, [(song, score), ...])]; a user
+        with fewer than K pairs gets a shorter list. Selected on the device."""
+        ds = self.dataset
+        ens, t = self._device_model(model)
+        songs, scores = ens.rank(t, K)
+        songs, scores = songs.cpu().numpy(), scores.cpu().numpy()
+        out = []
+        for u in range(ds.n_test):
+            n = int((songs[u] >= 0).sum())  # filled slots come first
+            out.append((ds.test_names(u), [(ds.song_names(int(s)), float(x))
+                                           for s, x in zip(songs[u, :n], scores[u, :n])]))
+        return out
+
+    def evaluateRanking(self, model: Union[str, Model, np.ndarray], k: int = 500) -> float:
+        """The challenge's mAP truncated at k over the model's ranked lists
+        (ranked and folded on the device, DeviceEnsemble.map_at)."""
+        ens, t = self._device_model(model)
+        return ens.map_at(t, k)
+
     def _from_model(self, model: Model) -> np.ndarray:
         ds = self.dataset
         sidx = {ds.song_names(i): i for i in range(ds.n_songs)}
