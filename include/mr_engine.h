@@ -495,6 +495,56 @@ int mr_rank_map_device(mr_ctx* ctx, const int32_t* songs_dev, int32_t K, int32_t
 int mr_rank_map_host(int32_t n_te, const int32_t* songs, int32_t K, int32_t k_eval, const int64_t* lab_off,
                      const int32_t* lab_songs, double* ap_out, double* map_out);
 
+/* ---- similar songs: item-item cosine rows and their top-K lists ---------------
+ * mr_similar_songs_device: cosineSimilarity(q, s) of MusicRecommender.scala:230-239
+ *   for n_q query songs against every song s of the context's shard
+ *   [song_lo, song_hi) — the function the ItemBasedModel sums over T(u)
+ *   (MR:249-257): the cosines of s against T(u) are the terms of rank(u, s).
+ *   Count:  C(q, s) = |L_tr(q) ∩ L_tr(s)|, the distinct TRAIN users who heard
+ *     both (MR:232-235; test users never count, a listener's repeated lines
+ *     count once).
+ *   Cosine: cos(q, s) = (double)C / (sqrt_c[q] * sqrt_c[s]), c(.) =
+ *     mr_dataset.song_count (train and test lines, duplicates counted, MR:237):
+ *     the host-computed sqrt(c) the scoring uses; a zero denominator gives 0.0
+ *     (MR:238). fp64 * and / only, no contraction: with the exact integer
+ *     numerator this is the IEEE operation sequence of MR:236-238, so the
+ *     values are bit-equal to the reference's own arithmetic.
+ *   query_songs: HOST, n_q global song ids in [0, n_songs), inside or outside
+ *     the shard, repeats allowed. A query without train listeners gives an
+ *     all-zero row and an empty list.
+ *   dense_dev (DEVICE, may be NULL): [n_q][song_hi - song_lo] doubles, always
+ *     fp64 whatever the context's out_dtype: every entry is cos(q_i, s), 0.0
+ *     included where no listener is shared; the entry s == q_i is NaN (the
+ *     reference skips s2 == song).
+ *   songs_dev [n_q][K] int32 / scores_dev [n_q][K] double (DEVICE; scores_dev
+ *     may be NULL): per query the K songs of the shard with C >= 1 and the
+ *     highest cosine, ordered by (cosine descending, global song id ascending)
+ *     as mr_rank_dense_device orders; the query itself and songs without a
+ *     common listener are never listed; missing slots hold song -1 / score NaN.
+ *   0 <= K <= MR_RANK_MAX_K: K = 0 computes rows only (dense_dev required,
+ *     songs_dev may be NULL); K >= 1 requires songs_dev. n_q >= 0; n_q = 0
+ *     succeeds without a launch.
+ *   Every argument is checked before any launch, in this order: MR_E_INVALID
+ *     for a NULL ctx, a bad K, n_q < 0, n_q > 0 with NULL query_songs or a
+ *     missing required buffer; MR_E_STATE before mr_load; MR_E_INVALID for a
+ *     query id out of range (no output is written). Synchronous on the context
+ *     stream.
+ *   The result is a pure function of the loaded dataset and the queries: it
+ *     does not depend on the launch shape (fused, separate, wide), block_songs,
+ *     train_order, ibm_route, or the song shard beyond which columns it holds.
+ *   Scratch is stream-ordered and bounded: the lists rank a scratch copy of
+ *     the rows (NaN where C = 0), and queries are processed in batches of at
+ *     most 65535 whose scratch rows fit MR_SIMILAR_SCRATCH_BYTES (one row at
+ *     least), plus 4 * n_q bytes for the query ids. mr_load uploads nothing
+ *     for this call: it reads the song -> listener transpose, the tile-major
+ *     train CSR and sqrt(c) that every launch shape holds.
+ *   Song shards: the per-shard lists of one query set (song ids are global)
+ *     merge with mr_rank_merge_host, n_te := n_q; the per-shard dense rows
+ *     concatenate by column. */
+#define MR_SIMILAR_SCRATCH_BYTES (256 << 20)
+int mr_similar_songs_device(mr_ctx* ctx, int32_t n_q, const int32_t* query_songs /* HOST, global ids */, int32_t K,
+                            int32_t* songs_dev, double* scores_dev, double* dense_dev);
+
 /* Kernel timing of mr_run calls made with opt.time_kernels = 1: per kernel
  * (0 = separate stage-1 kernel — neighbour lists —, 1 = the
  * scoring kernels — stage 2, fused stage 1, the in-launch top-k merge, the wide

@@ -197,6 +197,7 @@ SIGNATURES = {
                                    POINTER(c_double)]),
     "mr_rank_map_host": (c_int, [c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                  POINTER(c_double)]),
+    "mr_similar_songs_device": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "mr_last_error": (c_char_p, []),
     "mr_corpus_from_tsv": (c_int, [c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
     "mr_corpus_dataset": (c_int, [c_void_p, POINTER(MrDataset)]),

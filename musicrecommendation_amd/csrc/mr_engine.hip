@@ -5828,6 +5828,14 @@ int topk_records(mr_ctx* c, void** records, int64_t* rec_bytes) {
 
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 
+int similar_tables(mr_ctx* c, SimilarTables* out) {
+  if (!c || !out) return fail(MR_E_INVALID, "null argument");
+  if (!c->loaded) return fail(MR_E_STATE, "similar-song query before mr_load");
+  *out = SimilarTables{c->n_tr,       c->n_s,         c->song_lo, c->song_hi,  c->block_songs, c->n_tiles, c->opt.device,
+                       c->trs_off.p,  c->trs_users.p, c->toff.p,  c->tsongs.p, c->sqrt_c.p,    c->stream};
+  return MR_OK;
+}
+
 int set_device_share(mr_ctx* c, int n) {
   if (!c || n < 1) return fail(MR_E_INVALID, "set_device_share: null context or share < 1");
   c->dev_share = n;

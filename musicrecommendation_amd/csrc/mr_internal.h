@@ -38,6 +38,27 @@ int d2h_staged(mr_ctx* c, void* dst, size_t dpitch, const void* src, size_t spit
 // group's contexts measure free memory at once, before any of them allocates.
 int set_device_share(mr_ctx* c, int n);
 
+// The loaded tables a similar-song query reads (csrc/mr_similar.hip): device
+// pointers and geometry of the context's shard, valid until mr_load /
+// mr_destroy. MR_E_STATE before mr_load.
+struct SimilarTables {
+  int n_tr, n_s, song_lo, song_hi, block_songs, n_tiles, device;
+  const long long* trs_off;      // song -> train listeners CSR [n_s + 1] (every song, not only the shard's)
+  const int* trs_users;          //   listeners as the context's (renumbered) train users, ascending
+  const int* toff;               // tile-major train CSR over the shard [n_tiles * n_tr + 1]
+  const unsigned short* tsongs;  //   tile-local song ids, rows duplicate-free
+  const double* sqrt_c;          // sqrt(c(s)) [n_s] (train + test lines, duplicates counted)
+  void* stream;                  // the context's hipStream_t
+};
+int similar_tables(mr_ctx* c, SimilarTables* out);
+
+// k_rank_dense over n_rows rows of `width` values (f64 != 0: double, else
+// float; NaN = no entry) into songs / scores [n_rows][K] (scores may be NULL),
+// song id = song_lo + column: enqueued on `stream` (a hipStream_t), no host
+// wait; arguments are the caller's to check (csrc/mr_rank.hip).
+int rank_rows_async(void* stream, int f64, int32_t n_rows, int32_t width, int32_t song_lo, const void* dense,
+                    int32_t K, int32_t* songs, double* scores);
+
 // Set the calling thread's mr_last_error() message; returns code.
 int set_error(int code, const char* msg);
 

@@ -19,6 +19,9 @@
 // The histogram's LDS atomics only count (their sum does not depend on arrival
 // order); which entries are kept is decided by keys and column positions
 // alone, so the lists are a pure function of the row.
+// mr_internal::rank_rows_async enqueues the kernel over any n_rows rows of either
+// element type: mr_rank_dense_device ranks a model's rows through it, the
+// similar-song query (csrc/mr_similar.hip) its cosine rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +31,7 @@
 #include <vector>
 
 #include "mr_engine.h"
+#include "mr_internal.h"
 
 namespace mr_host {
 int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
@@ -360,6 +364,23 @@ double mean_ap(int n_te, const double* ap) {
 
 }  // namespace
 
+namespace mr_internal {
+
+int rank_rows_async(void* stream, int f64, int32_t n_rows, int32_t width, int32_t song_lo, const void* dense,
+                    int32_t K, int32_t* songs, double* scores) {
+  if (n_rows <= 0) return MR_OK;
+  hipStream_t st = (hipStream_t)stream;
+  RankParams rp{width, song_lo, K, dense, songs, scores};
+  if (f64)
+    hipLaunchKernelGGL(k_rank_dense<double>, dim3(n_rows), dim3(kRankThreads), 0, st, rp);
+  else
+    hipLaunchKernelGGL(k_rank_dense<float>, dim3(n_rows), dim3(kRankThreads), 0, st, rp);
+  MR_HIP(hipGetLastError());
+  return MR_OK;
+}
+
+}  // namespace mr_internal
+
 extern "C" {
 
 int mr_rank_dense_device(mr_ctx* ctx, const void* dense_dev, int32_t K, int32_t* songs_dev, double* scores_dev) {
@@ -370,14 +391,9 @@ int mr_rank_dense_device(mr_ctx* ctx, const void* dense_dev, int32_t K, int32_t*
   if (rc) return rc;
   MR_HIP(hipSetDevice(v.device));
   hipStream_t st = (hipStream_t)v.stream;
-  if (v.n_test_users > 0) {
-    RankParams rp{v.song_hi - v.song_lo, v.song_lo, K, dense_dev, songs_dev, scores_dev};
-    if (v.out_dtype == MR_OUT_F64)
-      hipLaunchKernelGGL(k_rank_dense<double>, dim3(v.n_test_users), dim3(kRankThreads), 0, st, rp);
-    else
-      hipLaunchKernelGGL(k_rank_dense<float>, dim3(v.n_test_users), dim3(kRankThreads), 0, st, rp);
-    MR_HIP(hipGetLastError());
-  }
+  if ((rc = mr_internal::rank_rows_async(st, v.out_dtype == MR_OUT_F64, v.n_test_users, v.song_hi - v.song_lo, v.song_lo,
+                                         dense_dev, K, songs_dev, scores_dev)))
+    return rc;
   MR_HIP(hipStreamSynchronize(st));
   return MR_OK;
 }

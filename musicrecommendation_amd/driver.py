@@ -3,7 +3,7 @@ MN:8-123, src/main/scala/distributed.scala DS:55-602) on the MI355X engine.
 
     python -m musicrecommendation_amd.driver TRAIN_N TEST_N [--resources DIR]
         [--devices 0,1,...] [--song-shards G_s] [--user-blocks G_u] [--distributed] [--quiet]
-        [--sweep KIND:LO:HI:N ...] [--recommend K[:PATH]]
+        [--sweep KIND:LO:HI:N ...] [--recommend K[:PATH]] [--similar K[:PATH]]
 
 Same flow and output as main.scala: load train_{N}_{M}.txt, test_{N}_{M}.txt,
 test_labels_{N}_{M}.txt (MN:21-23), build the recommender (untimed, MN:27),
@@ -37,6 +37,13 @@ device (DeviceEnsemble.rank), and prints each model's mAP truncated at K — the
 Million Song Dataset Challenge's metric at K = 500 — beside the threshold
 mAPs. With PATH the linear-combination model's lists are written there, one
 "user<TAB>song<TAB>score" line per recommendation in (user, rank) order.
+
+--similar K[:PATH] (K <= 1024) answers, after the flow, which songs are most
+like each distinct song the test users have heard — the cosineSimilarity rows
+(MR:230-239) the ItemBasedModel consumes: per such song the K songs with the
+highest cosine over common train listeners (DeviceEnsemble.similar_songs). It
+prints the query count and the time; with PATH the lists are written there,
+one "song<TAB>other<TAB>cosine" line per entry in (song, rank) order.
 """
 from __future__ import annotations
 
@@ -113,6 +120,15 @@ def parse_recommend(spec) -> Tuple[int, Optional[str]]:
     return k, (os.fspath(path) if path is not None else None)
 
 
+def parse_similar(spec) -> Tuple[int, Optional[str]]:
+    """--similar K[:PATH] (or an int K, or (K, PATH)) -> (K, path or None),
+    parsed like --recommend; ValueError on a bad spec."""
+    try:
+        return parse_recommend(spec)
+    except ValueError as e:
+        raise ValueError(str(e).replace("--recommend", "--similar", 1)) from None
+
+
 def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
     """N evenly spaced values LO + i*(HI-LO)/(N-1) (N = 1: LO alone)."""
     return [lo + i * (hi - lo) / (n - 1) for i in range(n)] if n > 1 else [lo]
@@ -120,7 +136,7 @@ def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
 
 def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[int]] = None,
         song_shards: Optional[int] = None, user_blocks: int = 1, verbose: bool = True, seed: int = 1,
-        distributed: bool = False, sweeps: Optional[Sequence[str]] = None, recommend=None) -> dict:
+        distributed: bool = False, sweeps: Optional[Sequence[str]] = None, recommend=None, similar=None) -> dict:
     import numpy as np
 
     from .dataset import Dataset
@@ -129,6 +145,7 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
 
     specs = [parse_sweep(s) if isinstance(s, str) else tuple(s) for s in (sweeps or [])]  # before any work
     rec = parse_recommend(recommend) if recommend is not None else None
+    sim = parse_similar(similar) if similar is not None else None
 
     n_thr = 11 if distributed else 10  # DS:395 vs MR:590
     if song_shards is None:  # one song shard per listed GPU and user block (DS:477-479's song partition)
@@ -201,6 +218,21 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
         b = best(params, vals)
         print(f"{kind} sweep best: {b} mAP: {round_at(10, vals[params.index(b)])}", flush=True)
         swept.append({"kind": kind, "params": params, "mAP": vals, "best": b})
+    n_sim = 0
+    if sim is not None:
+        from . import modelio
+
+        sk, spath = sim
+        queries = np.unique(np.asarray(ds.te_songs, dtype=np.int32))  # every song of some T(u)
+        n_sim = int(queries.size)
+        print(f"similar-song queries: {n_sim}", flush=True)
+        lists = timed(lambda: ens.similar_songs(queries, sk), f"top-{sk} similar songs of {n_sim} songs", verbose)
+        if spath is not None:
+            songs, scores = lists[0].cpu().numpy(), lists[1].cpu().numpy()
+            modelio.write_recommendations(spath, [
+                (ds.song_names(int(q)), [(ds.song_names(int(g)), float(x))
+                                         for g, x in zip(songs[i], scores[i]) if g >= 0])
+                for i, q in enumerate(queries)])
     eng.close()
     out = {"mAP": maps, "multi_gpu_checked": group_checked, "thresholds": n_thr,
            "layout": (song_shards, user_blocks)}
@@ -209,6 +241,8 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
     if rec is not None:
         out["mAP@K"] = ranked
         out["recommend"] = {"K": rec[0], "path": rec[1]}
+    if sim is not None:
+        out["similar"] = {"K": sim[0], "path": sim[1], "queries": n_sim}
     return out
 
 
@@ -222,6 +256,13 @@ def _sweep_arg(spec: str) -> Tuple[str, float, float, int]:
 def _recommend_arg(spec: str) -> Tuple[int, Optional[str]]:
     try:
         return parse_recommend(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _similar_arg(spec: str) -> Tuple[int, Optional[str]]:
+    try:
+        return parse_similar(spec)
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e)) from None
 
@@ -245,11 +286,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--recommend", default=None, metavar="K[:PATH]", type=_recommend_arg,
                     help="after the flow, rank the K best songs per test user of each model (K <= 1024), print "
                          "each model's mAP@K, and write the linear-combination model's lists to PATH")
+    ap.add_argument("--similar", default=None, metavar="K[:PATH]", type=_similar_arg,
+                    help="after the flow, the K songs most like each distinct song the test users have heard "
+                         "(K <= 1024; cosine over common train listeners); the lists are written to PATH")
     a = ap.parse_args(argv)
     devices = [int(x) for x in a.devices.split(",") if x.strip()] if a.devices else None
     train_n = a.train_n if a.train_n is not None else (300 if a.distributed else 100)
     run(train_n, a.test_n, a.resources, devices, a.song_shards, a.user_blocks, verbose=not a.quiet, seed=a.seed,
-        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend)
+        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend, similar=a.similar)
     return 0
 
 

@@ -405,6 +405,21 @@ class Engine:
                    "mr_rank_map_device")
         return out.value, ap[:self.n_test]
 
+    # ---- similar songs (mr_similar_songs_device) --------------------------------
+    def similar_songs(self, queries, K: int, songs_ptr: int, scores_ptr: int = 0, dense_ptr: int = 0) -> None:
+        """cosineSimilarity (MR:230-239) of the query songs (global ids, host)
+        against this engine's shard into caller-owned device buffers: songs
+        int32 [n_q][K] and scores float64 [n_q][K] (0: none) — the K songs with
+        a common train listener and the highest cosine by (cosine desc, song
+        asc), -1 / NaN padding — and dense float64 [n_q][width] rows (0: none;
+        required for K = 0); synchronous (mr_similar_songs_device)."""
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        _lib.check(self._L.mr_similar_songs_device(self._h, int(q.shape[0]), q.ctypes.data_as(ctypes.c_void_p), int(K),
+                                                   ctypes.c_void_p(songs_ptr or None),
+                                                   ctypes.c_void_p(scores_ptr or None),
+                                                   ctypes.c_void_p(dense_ptr or None)),
+                   "mr_similar_songs_device")
+
     def timing_begin(self) -> None:
         """Open a timing window (one event on the engine stream)."""
         _lib.check(self._L.mr_timing_begin(self._h), "mr_timing_begin")

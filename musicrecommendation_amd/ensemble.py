@@ -25,6 +25,10 @@ rank / map_at give what the scores are for: per test user the K <= 1024 best
 songs of any dense model by (score desc, song asc) — a radix select and an LDS
 sort per user (csrc/mr_rank.hip), negative scores included — and the mAP
 truncated at k over such lists, folded on the device in a fixed order.
+
+similar_songs answers the item-based recommender's own question — which songs
+are most like this one: the cosine rows of MR:230-239 for query songs
+(csrc/mr_similar.hip) and their K best entries.
 """
 from __future__ import annotations
 
@@ -389,6 +393,29 @@ class DeviceEnsemble:
         self._after_torch()
         self.e.rank_dense(t.data_ptr(), K, songs.data_ptr(), scores.data_ptr())
         return songs, scores
+
+    # ---- similar songs (mr_similar_songs_device) ----------------------------------
+    def similar_songs(self, queries, K: int = 10, dense: bool = False):
+        """Per query song (global ids) the K songs of the engine's shard most
+        like it: cosineSimilarity of MR:230-239 over common train listeners, by
+        (cosine desc, global song id asc), as device tensors (songs int32,
+        scores float64), each n_q x K; songs without a common listener and the
+        query itself are never listed, empty slots hold -1 / NaN. With dense
+        also the n_q x width float64 cosine rows (0.0 included, NaN at the
+        query's own column): (songs, scores, rows). K = 0 needs dense."""
+        import torch
+
+        K = int(K)
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        songs = torch.empty((q.shape[0], K), dtype=torch.int32, device=self.device)
+        scores = torch.empty((q.shape[0], K), dtype=torch.float64, device=self.device)
+        rows = torch.empty((q.shape[0], self.e.width), dtype=torch.float64, device=self.device) if dense else None
+        if q.shape[0] == 0:  # nothing to launch (and empty tensors have no address to pass)
+            return (songs, scores, rows) if dense else (songs, scores)
+        self._after_torch()
+        self.e.similar_songs(q, K, songs.data_ptr() if K > 0 else 0, scores.data_ptr() if K > 0 else 0,
+                             rows.data_ptr() if dense else 0)
+        return (songs, scores, rows) if dense else (songs, scores)
 
     def map_at(self, lists_or_model, k: int, K: Optional[int] = None) -> float:
         """The challenge's truncated mAP@k (evaluation.map_at_k's definition in

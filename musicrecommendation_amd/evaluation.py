@@ -10,6 +10,9 @@
 * ``rank_lists`` — the numpy restatement of the engine's full ranked lists
   (mr_rank_dense_device): per user the K best valid entries by (value desc,
   song id asc).
+* ``song_similarity`` / ``similar_lists`` — the numpy restatement of the
+  similar-song query (mr_similar_songs_device): the reference's
+  cosineSimilarity (MR:230-239) rows of query songs and their top-K lists.
 Vectorised over the dense n_test x n_songs score matrix (NaN = no pair).
 """
 from __future__ import annotations
@@ -140,3 +143,51 @@ def rank_lists(dense: np.ndarray, K: int, song_lo: int = 0):
         songs[u, :order.size] = cols[order] + song_lo
         scores[u, :order.size] = vals[order]
     return songs, scores
+
+
+def song_similarity(ds: Dataset, queries, song_lo: int = 0, song_hi=None) -> np.ndarray:
+    """cosineSimilarity(q, s) (MR:230-239) of every query song (global ids,
+    repeats allowed) against the songs [song_lo, song_hi): float64 rows
+    len(queries) x (song_hi - song_lo). The numerator is the number of distinct
+    train users who heard both (from the train CSR: test users never count,
+    repeated lines count once); the value is num / (sqrt(c(q)) * sqrt(c(s)))
+    with c = song_count (train and test lines, duplicates counted), 0.0 for a
+    zero denominator; the entry s == q is NaN (the reference skips s2 == song).
+    The numpy twin of mr_similar_songs_device's dense rows, the CPU definition
+    the device is compared against bit for bit."""
+    song_hi = ds.n_songs if song_hi is None else int(song_hi)
+    song_lo = int(song_lo)
+    q = np.asarray(queries, dtype=np.int64).reshape(-1)
+    if q.size and (q.min() < 0 or q.max() >= ds.n_songs):
+        raise ValueError("song_similarity: query ids must be in [0, n_songs)")
+    if not 0 <= song_lo <= song_hi <= ds.n_songs:
+        raise ValueError("song_similarity: bad song range")
+    tr_off = np.asarray(ds.tr_off, dtype=np.int64)
+    tr_songs = np.asarray(ds.tr_songs, dtype=np.int64)
+    users = np.repeat(np.arange(ds.n_train, dtype=np.int64), np.diff(tr_off))
+    sq = np.sqrt(np.asarray(ds.song_count, dtype=np.float64))
+    out = np.empty((q.size, song_hi - song_lo), dtype=np.float64)
+    rows = {}
+    for i, qs in enumerate(q.tolist()):
+        if qs not in rows:
+            heard = np.zeros(ds.n_train, dtype=bool)
+            heard[users[tr_songs == qs]] = True             # L_tr(q)
+            num = np.bincount(tr_songs[heard[users]], minlength=ds.n_songs)[song_lo:song_hi].astype(np.float64)
+            den = np.sqrt(np.float64(ds.song_count[qs])) * sq[song_lo:song_hi]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                row = np.where(den != 0, num / den, 0.0)
+            if song_lo <= qs < song_hi:
+                row[qs - song_lo] = np.nan
+            rows[qs] = row
+        out[i] = rows[qs]
+    return out
+
+
+def similar_lists(dense_rows: np.ndarray, K: int, song_lo: int = 0):
+    """(songs int32, scores float64), each n_queries x K, from song_similarity
+    rows: the songs with a non-zero cosine (a common train listener) in
+    rank_lists' order (cosine desc, song id asc); -1 / NaN padding. The numpy
+    twin of mr_similar_songs_device's lists."""
+    d = np.array(dense_rows, dtype=np.float64, copy=True)
+    d[d == 0] = np.nan  # no common listener: never listed
+    return rank_lists(d, K, song_lo)

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import os
 import tempfile
-from typing import Iterable, List, Optional, Tuple, Union
+from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -234,6 +234,54 @@ class MusicRecommender:
         (ranked and folded on the device, DeviceEnsemble.map_at)."""
         ens, t = self._device_model(model)
         return ens.map_at(t, k)
+
+    # ---- similar songs (DeviceEnsemble.similar_songs) -------------------------------
+    def _song_index(self) -> dict:
+        if getattr(self, "_sidx", None) is None:
+            ds = self.dataset
+            self._sidx = {ds.song_names(i): i for i in range(ds.n_songs)}
+        return self._sidx
+
+    def similarSongs(self, songs: Sequence[str], K: int = 10) -> List[Tuple[str, List[Tuple[str, float]]]]:
+        """Per given song (in the given order) the K songs most like it by the
+        reference's cosineSimilarity (MR:230-239), ordered (cosine desc, song
+        asc), by name: [(song, [(other, cosine), ...])] — recommend()'s shape;
+        songs without a common train listener are not listed. An unknown name
+        raises KeyError. Computed on the device."""
+        from .ensemble import DeviceEnsemble
+
+        ds = self.dataset
+        sidx = self._song_index()
+        names = list(songs)
+        q = [sidx[n] for n in names]
+        ids, cos = DeviceEnsemble(self.engine()).similar_songs(q, K)
+        ids, cos = ids.cpu().numpy(), cos.cpu().numpy()
+        return [(name, [(ds.song_names(int(s)), float(x)) for s, x in zip(ids[i], cos[i]) if s >= 0])
+                for i, name in enumerate(names)]
+
+    def explain(self, user: str, song: str) -> List[Tuple[str, float]]:
+        """Where the item-based rank(user, song) comes from: [(s2,
+        cosineSimilarity(song, s2))] over the songs s2 of T(user) with a
+        non-zero cosine — the terms of MR:249-257 — ordered (cosine desc, song
+        name asc). One device query for `song`, then a gather of the columns
+        T(user). ValueError when the user has heard `song`: the reference
+        emits no such pair (MR:109). Unknown names raise KeyError."""
+        from .ensemble import DeviceEnsemble
+
+        ds = self.dataset
+        s = self._song_index()[song]
+        users = {ds.test_names(i): i for i in range(ds.n_test)}
+        u = users[user]
+        heard = np.asarray(ds.te_songs[ds.te_off[u]:ds.te_off[u + 1]], dtype=np.int64)
+        if s in heard:
+            raise ValueError(f"user {user!r} has heard {song!r}: the reference emits no such pair (MR:109)")
+        import torch
+
+        ens = DeviceEnsemble(self.engine())
+        rows = ens.similar_songs([s], 0, dense=True)[2]
+        cos = rows[0, torch.from_numpy(heard).to(rows.device)].cpu().numpy()
+        terms = [(ds.song_names(int(s2)), float(x)) for s2, x in zip(heard, cos) if x != 0.0]
+        return sorted(terms, key=lambda t: (-t[1], t[0]))
 
     def _from_model(self, model: Model) -> np.ndarray:
         ds = self.dataset
