@@ -545,6 +545,55 @@ int mr_rank_map_host(int32_t n_te, const int32_t* songs, int32_t K, int32_t k_ev
 int mr_similar_songs_device(mr_ctx* ctx, int32_t n_q, const int32_t* query_songs /* HOST, global ids */, int32_t K,
                             int32_t* songs_dev, double* scores_dev, double* dense_dev);
 
+/* ---- asymmetric-cosine, locality-q item-based model ----------------------------
+ * The neighbourhood method of the Million Song Dataset Challenge literature: the
+ * ItemBasedModel (MR:230-257) with two knobs on the similarity, an asymmetry
+ * exponent alpha in [0, 1] that splits the popularity normalisation between
+ * the candidate s and the heard song s2, and a locality exponent q in
+ * [1, MR_ASYM_MAX_Q] applied to every similarity before the sum. At alpha =
+ * 0.5, q = 1 it is the reference's model.
+ * mr_asym_tables (HOST only, no GPU): pow_a[i] = c^alpha, pow_b[i] =
+ *   c^(1-alpha) for cd = (double)counts[i], i < n: std::pow(cd, alpha) and
+ *   std::pow(cd, 1.0 - alpha) in general, and exactly
+ *     alpha == 0.5: both std::sqrt(cd) (the scoring's own sqrt(c) values),
+ *     alpha == 0.0: pow_a = 1.0, pow_b = cd,
+ *     alpha == 1.0: pow_a = cd,  pow_b = 1.0.
+ *   MR_E_INVALID for alpha outside [0, 1] or NaN, n < 0 or a NULL pointer. The
+ *   device never evaluates pow: it reads these tables, and so does the numpy
+ *   twin (evaluation.asym_item_model), whatever libm either links against.
+ * mr_ibm_asym_device: for every test user u of the context and every song s
+ *   of its shard [song_lo, song_hi)
+ *   Weight:   w(s, s2) = (double)C(s, s2) / (pow_a[s] * pow_b[s2]), C =
+ *     |L_tr(s) ∩ L_tr(s2)| the distinct TRAIN users who heard both
+ *     (mr_similar_songs_device's counts), the tables those of mr_asym_tables
+ *     over mr_dataset.song_count; a zero denominator gives 0.0. alpha is the
+ *     candidate's share: alpha = 0 gives C / c(s2), alpha = 1 gives C / c(s).
+ *   Locality: t = w, then q - 1 times t = t * w (fp64, no pow, no contraction).
+ *   Score:    score(u, s) = the left fold from +0.0 of acc = acc + t(s, s2)
+ *     over s2 in T(u) in ascending song id (terms with C = 0 are +0.0 and
+ *     change no bit); NaN for s in T(u), as in every dense model here.
+ *   dense_dev: caller-owned DEVICE buffer of n_te x (song_hi - song_lo)
+ *     elements of the context's out_dtype (f32: the fp64 score rounded once).
+ *   Every argument is checked before any launch, in this order: MR_E_INVALID
+ *     for a NULL ctx, alpha outside [0, 1] or NaN, q outside
+ *     [1, MR_ASYM_MAX_Q], a NULL dense_dev; MR_E_STATE before mr_load (no
+ *     output is written). Synchronous on the context stream.
+ *   The result is a pure function of the loaded dataset, alpha, q and the
+ *     columns the shard holds: it does not depend on the launch shape,
+ *     block_songs, train_order, ibm_route or the sub-range size. Song shards
+ *     concatenate by column. At (0.5, 1) every value is bit-equal to the
+ *     sequential fold of mr_similar_songs_device's rows of T(u), and within the
+ *     literal-versus-fixed-point bound (1e-7 relative) of mr_run's MR_IBM.
+ *   mr_load keeps a host copy of song_count (4 * n_songs bytes) and uploads
+ *     nothing for this call; each call uploads its two tables (16 * n_songs
+ *     bytes) into stream-ordered scratch. One 1024-thread workgroup per (song
+ *     sub-range of at most 8192 songs, test user) walks the train listeners of
+ *     every s2 in T(u) (csrc/mr_asym.hip). MR_ASYM_SUB=n (64..8192) in the
+ *     environment lowers the sub-range size (diagnostic; results identical). */
+#define MR_ASYM_MAX_Q 8
+int mr_asym_tables(double alpha, int32_t n, const int32_t* counts, double* pow_a, double* pow_b); /* host only */
+int mr_ibm_asym_device(mr_ctx* ctx, double alpha, int32_t q, void* dense_dev);
+
 /* Kernel timing of mr_run calls made with opt.time_kernels = 1: per kernel
  * (0 = separate stage-1 kernel — neighbour lists —, 1 = the
  * scoring kernels — stage 2, fused stage 1, the in-launch top-k merge, the wide

@@ -120,6 +120,7 @@ MR_COMB_AGGREGATION = 1
 MR_COMB_STOCHASTIC = 2
 MR_SWEEP_MAX_PARAMS = 64
 MR_RANK_MAX_K = 1024
+MR_ASYM_MAX_Q = 8
 
 
 class EngineError(RuntimeError):
@@ -198,6 +199,8 @@ SIGNATURES = {
     "mr_rank_map_host": (c_int, [c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                  POINTER(c_double)]),
     "mr_similar_songs_device": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mr_asym_tables": (c_int, [c_double, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mr_ibm_asym_device": (c_int, [c_void_p, c_double, c_int32, c_void_p]),
     "mr_last_error": (c_char_p, []),
     "mr_corpus_from_tsv": (c_int, [c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
     "mr_corpus_dataset": (c_int, [c_void_p, POINTER(MrDataset)]),

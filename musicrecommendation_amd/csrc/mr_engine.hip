@@ -3957,6 +3957,7 @@ struct mr_ctx {
   DevBuf<unsigned> counter;
   DevBuf<double> sqrt_c, sqrt_tr, sqrt_te, top_score;
   DevBuf<float> rsq_c;  // wide shape: 1 / sqrt(c(s)) as fp32 (wide_cand_topk's approximations)
+  std::vector<int32_t> song_count;  // host copy of mr_dataset.song_count (mr_ibm_asym_device's tables)
   bool cand_on = false; // wide shape, top-k only: the candidate-only tile top-k (MR_WIDE_CAND=0: off)
   DevBuf<unsigned char> dense;
   DevBuf<long long> stamps;
@@ -4015,6 +4016,7 @@ struct mr_ctx {
     counter.release();
     sqrt_c.release(); sqrt_tr.release(); sqrt_te.release(); top_score.release();
     rsq_c.release(); cand_on = false;
+    song_count = std::vector<int32_t>();
     dense.release();
     mm_key.release(); mm_on = mm_valid = false;
     stamps.release();
@@ -5299,6 +5301,7 @@ int mr_load(mr_ctx* c, const mr_dataset* d) {
   c->block_songs = lp.block_songs; c->n_tiles = lp.n_tiles;
   c->cap = lp.cap; c->batch = lp.batch;
   c->chunk = lp.chunk; c->n_chunks = lp.n_chunks;
+  c->song_count.assign(d->song_count, d->song_count + n_s);
   c->loaded = true;
   c->ran = false;
   return MR_OK;
@@ -5833,6 +5836,19 @@ int similar_tables(mr_ctx* c, SimilarTables* out) {
   if (!c->loaded) return fail(MR_E_STATE, "similar-song query before mr_load");
   *out = SimilarTables{c->n_tr,       c->n_s,         c->song_lo, c->song_hi,  c->block_songs, c->n_tiles, c->opt.device,
                        c->trs_off.p,  c->trs_users.p, c->toff.p,  c->tsongs.p, c->sqrt_c.p,    c->stream};
+  return MR_OK;
+}
+
+int asym_tables(mr_ctx* c, AsymTables* out) {
+  if (!c || !out) return fail(MR_E_INVALID, "null argument");
+  if (!c->loaded) return fail(MR_E_STATE, "asymmetric item-based model before mr_load");
+  int rc = similar_tables(c, &out->sim);
+  if (rc) return rc;
+  out->n_te = c->n_te;
+  out->f64 = c->opt.out_dtype == MR_OUT_F64;
+  out->te_off = c->te_off.p;
+  out->te_songs = c->te_songs.p;
+  out->song_count = c->song_count.data();
   return MR_OK;
 }
 

@@ -52,6 +52,19 @@ struct SimilarTables {
 };
 int similar_tables(mr_ctx* c, SimilarTables* out);
 
+// The same tables plus what the asymmetric item-based model reads
+// (csrc/mr_asym.hip): the test users' CSR on the device, the context's output
+// element type and the HOST copy of mr_dataset.song_count that mr_load keeps
+// (4 * n_s bytes). Valid until mr_load / mr_destroy. MR_E_STATE before mr_load.
+struct AsymTables {
+  SimilarTables sim;
+  int n_te, f64;               // f64 != 0: the dense model is double, else float
+  const long long* te_off;     // device: test user -> distinct visible songs T(u) [n_te + 1]
+  const int* te_songs;         //   ascending song ids
+  const int32_t* song_count;   // host: c(s) [n_s]
+};
+int asym_tables(mr_ctx* c, AsymTables* out);
+
 // k_rank_dense over n_rows rows of `width` values (f64 != 0: double, else
 // float; NaN = no entry) into songs / scores [n_rows][K] (scores may be NULL),
 // song id = song_lo + column: enqueued on `stream` (a hipStream_t), no host

@@ -3,7 +3,7 @@ MN:8-123, src/main/scala/distributed.scala DS:55-602) on the MI355X engine.
 
     python -m musicrecommendation_amd.driver TRAIN_N TEST_N [--resources DIR]
         [--devices 0,1,...] [--song-shards G_s] [--user-blocks G_u] [--distributed] [--quiet]
-        [--sweep KIND:LO:HI:N ...] [--recommend K[:PATH]] [--similar K[:PATH]]
+        [--sweep KIND:LO:HI:N ...] [--recommend K[:PATH]] [--similar K[:PATH]] [--asym ALPHA:Q]
 
 Same flow and output as main.scala: load train_{N}_{M}.txt, test_{N}_{M}.txt,
 test_labels_{N}_{M}.txt (MN:21-23), build the recommender (untimed, MN:27),
@@ -44,6 +44,12 @@ like each distinct song the test users have heard — the cosineSimilarity rows
 highest cosine over common train listeners (DeviceEnsemble.similar_songs). It
 prints the query count and the time; with PATH the lists are written there,
 one "song<TAB>other<TAB>cosine" line per entry in (song, rank) order.
+
+--asym ALPHA:Q (ALPHA in [0, 1], Q in 1..8) adds a sixth model to the run,
+asymmetricItemBasedModel: the item-based model with the similarity C /
+(c(s)^ALPHA * c(s2)^(1-ALPHA)) raised to the power Q before the sum over T(u)
+(DeviceEnsemble.item_based; 0.5:1 is the reference's model summed in fp64),
+timed, evaluated and, with --recommend, ranked like the others.
 """
 from __future__ import annotations
 
@@ -129,6 +135,29 @@ def parse_similar(spec) -> Tuple[int, Optional[str]]:
         raise ValueError(str(e).replace("--recommend", "--similar", 1)) from None
 
 
+def parse_asym(spec) -> Tuple[float, int]:
+    """--asym ALPHA:Q (or (alpha, q)) -> (alpha, q); ValueError on a bad spec."""
+    from ._lib import MR_ASYM_MAX_Q
+
+    if isinstance(spec, (tuple, list)):
+        if len(spec) != 2:
+            raise ValueError(f"--asym {spec!r}: expected ALPHA:Q")
+        a, q = spec
+    else:
+        a, sep, q = str(spec).partition(":")
+        if not sep:
+            raise ValueError(f"--asym {spec!r}: expected ALPHA:Q")
+    try:
+        a, q = float(a), int(q)
+    except (TypeError, ValueError):
+        raise ValueError(f"--asym {spec!r}: ALPHA is a number, Q an integer") from None
+    if not 0.0 <= a <= 1.0:  # NaN fails both comparisons
+        raise ValueError(f"--asym {spec!r}: ALPHA must be in [0, 1]")
+    if not 1 <= q <= MR_ASYM_MAX_Q:
+        raise ValueError(f"--asym {spec!r}: Q must be in [1, {MR_ASYM_MAX_Q}]")
+    return a, q
+
+
 def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
     """N evenly spaced values LO + i*(HI-LO)/(N-1) (N = 1: LO alone)."""
     return [lo + i * (hi - lo) / (n - 1) for i in range(n)] if n > 1 else [lo]
@@ -136,7 +165,8 @@ def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
 
 def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[int]] = None,
         song_shards: Optional[int] = None, user_blocks: int = 1, verbose: bool = True, seed: int = 1,
-        distributed: bool = False, sweeps: Optional[Sequence[str]] = None, recommend=None, similar=None) -> dict:
+        distributed: bool = False, sweeps: Optional[Sequence[str]] = None, recommend=None, similar=None,
+        asym=None) -> dict:
     import numpy as np
 
     from .dataset import Dataset
@@ -146,6 +176,7 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
     specs = [parse_sweep(s) if isinstance(s, str) else tuple(s) for s in (sweeps or [])]  # before any work
     rec = parse_recommend(recommend) if recommend is not None else None
     sim = parse_similar(similar) if similar is not None else None
+    asy = parse_asym(asym) if asym is not None else None
 
     n_thr = 11 if distributed else 10  # DS:395 vs MR:590
     if song_shards is None:  # one song shard per listed GPU and user block (DS:477-479's song partition)
@@ -185,9 +216,14 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
     lcm = timed(lambda: ens.linear(ubm, ibm, 0.5), "linear-combination model", verbose)          # MN:62-69
     am = timed(lambda: ens.aggregation(ubm, ibm, 0.5), "aggregation model", verbose)             # MN:70-77
     scm = timed(lambda: ens.stochastic(ubm, ibm, 0.5, seed=seed), "stochastic-combination model", verbose)
+    models = [("user-based", ubm), ("item-based", ibm), ("linear-combination", lcm), ("aggregation", am),
+              ("stochastic-combination", scm)]
+    if asy is not None:
+        models.append(("asymmetricItemBasedModel",
+                       timed(lambda: ens.item_based(*asy), f"asymmetricItemBasedModel (alpha {asy[0]}, q {asy[1]})",
+                             verbose)))
     maps = {}
-    for name, t in (("user-based", ubm), ("item-based", ibm), ("linear-combination", lcm), ("aggregation", am),
-                    ("stochastic-combination", scm)):
+    for name, t in models:
         maps[name] = timed(lambda: ens.threshold_map(t, n_thresholds=n_thr), f"{name} model mAP", verbose)  # MN:101-110
     for name, v in maps.items():
         print(f"{name} model mAP: {round_at(10, v)}", flush=True)                              # MN:112-121
@@ -196,8 +232,7 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
         from . import modelio
 
         rk, rpath = rec
-        for name, t in (("user-based", ubm), ("item-based", ibm), ("linear-combination", lcm), ("aggregation", am),
-                        ("stochastic-combination", scm)):
+        for name, t in models:
             lists = timed(lambda: ens.rank(t, rk), f"{name} model top-{rk} lists", verbose)
             ranked[name] = ens.map_at(lists, rk)
             if rpath is not None and name == "linear-combination":
@@ -241,6 +276,8 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
     if rec is not None:
         out["mAP@K"] = ranked
         out["recommend"] = {"K": rec[0], "path": rec[1]}
+    if asy is not None:
+        out["asym"] = {"alpha": asy[0], "q": asy[1]}
     if sim is not None:
         out["similar"] = {"K": sim[0], "path": sim[1], "queries": n_sim}
     return out
@@ -267,6 +304,13 @@ def _similar_arg(spec: str) -> Tuple[int, Optional[str]]:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _asym_arg(spec: str) -> Tuple[float, int]:
+    try:
+        return parse_asym(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("train_n", type=int, nargs="?", default=None)  # MN:15 default 100 (DS:61: 300)
@@ -289,11 +333,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--similar", default=None, metavar="K[:PATH]", type=_similar_arg,
                     help="after the flow, the K songs most like each distinct song the test users have heard "
                          "(K <= 1024; cosine over common train listeners); the lists are written to PATH")
+    ap.add_argument("--asym", default=None, metavar="ALPHA:Q", type=_asym_arg,
+                    help="add the asymmetric-cosine (ALPHA in [0, 1]), locality-Q (1..8) item-based model to the run "
+                         "as asymmetricItemBasedModel")
     a = ap.parse_args(argv)
     devices = [int(x) for x in a.devices.split(",") if x.strip()] if a.devices else None
     train_n = a.train_n if a.train_n is not None else (300 if a.distributed else 100)
     run(train_n, a.test_n, a.resources, devices, a.song_shards, a.user_blocks, verbose=not a.quiet, seed=a.seed,
-        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend, similar=a.similar)
+        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend, similar=a.similar, asym=a.asym)
     return 0
 
 

@@ -420,6 +420,16 @@ class Engine:
                                                    ctypes.c_void_p(dense_ptr or None)),
                    "mr_similar_songs_device")
 
+    # ---- asymmetric-cosine, locality-q item-based model (mr_ibm_asym_device) -----
+    def ibm_asym(self, alpha: float, q: int, dense_ptr: int) -> None:
+        """The item-based model with similarity (C / (c(s)^alpha *
+        c(s2)^(1-alpha)))^q, summed over T(u) in ascending song id, into a
+        caller-owned device buffer (n_test x width of this engine's dtype, NaN
+        for heard songs); alpha = 0.5, q = 1 is the reference's model;
+        synchronous (mr_ibm_asym_device)."""
+        _lib.check(self._L.mr_ibm_asym_device(self._h, float(alpha), int(q), ctypes.c_void_p(dense_ptr or None)),
+                   "mr_ibm_asym_device")
+
     def timing_begin(self) -> None:
         """Open a timing window (one event on the engine stream)."""
         _lib.check(self._L.mr_timing_begin(self._h), "mr_timing_begin")

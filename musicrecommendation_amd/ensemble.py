@@ -29,6 +29,11 @@ truncated at k over such lists, folded on the device in a fixed order.
 similar_songs answers the item-based recommender's own question — which songs
 are most like this one: the cosine rows of MR:230-239 for query songs
 (csrc/mr_similar.hip) and their K best entries.
+
+item_based gives that similarity its two knobs, the asymmetry exponent alpha
+and the locality exponent q of the Million Song Dataset Challenge's
+neighbourhood method (csrc/mr_asym.hip); its result is a dense model like
+model("ibm").
 """
 from __future__ import annotations
 
@@ -155,6 +160,19 @@ class DeviceEnsemble:
         mm = self.e.dense_minmax()  # the scoring kernels' min / max (wide shape), for threshold_map
         if mm is not None:
             t._mr_minmax = (t._version, mm[0], mm[1])
+        return t
+
+    def item_based(self, alpha: float = 0.5, q: int = 1):
+        """The asymmetric-cosine, locality-q item-based model into a new device
+        tensor (mr_ibm_asym_device, csrc/mr_asym.hip): score(u, s) = the sum
+        over s2 in T(u), ascending, of (C(s, s2) / (c(s)^alpha *
+        c(s2)^(1-alpha)))^q, computed literally in fp64 from the co-listening
+        counts. The defaults give the reference's ItemBasedModel (within 1e-7
+        relative of model("ibm"), which sums in fixed point). A model like any
+        other: rank, map_at, threshold_map and the combinations accept it."""
+        t = self.empty()
+        self._after_torch()
+        self.e.ibm_asym(alpha, q, t.data_ptr())
         return t
 
     def _combine(self, kind: int, ubm, ibm, param: float, seed: int = 0):

@@ -13,6 +13,9 @@
 * ``song_similarity`` / ``similar_lists`` — the numpy restatement of the
   similar-song query (mr_similar_songs_device): the reference's
   cosineSimilarity (MR:230-239) rows of query songs and their top-K lists.
+* ``asym_item_model`` — the numpy restatement of the asymmetric-cosine,
+  locality-q item-based model (mr_ibm_asym_device), tables from the library's
+  host-only mr_asym_tables.
 Vectorised over the dense n_test x n_songs score matrix (NaN = no pair).
 """
 from __future__ import annotations
@@ -180,6 +183,80 @@ def song_similarity(ds: Dataset, queries, song_lo: int = 0, song_hi=None) -> np.
                 row[qs - song_lo] = np.nan
             rows[qs] = row
         out[i] = rows[qs]
+    return out
+
+
+def asym_tables(alpha: float, counts) -> tuple:
+    """(pow_a, pow_b) = (c^alpha, c^(1-alpha)) as float64 arrays from the
+    engine library's host-only mr_asym_tables (it loads without a GPU): the
+    very values the device reads, so the twin below does not depend on the libm
+    numpy links against."""
+    import ctypes
+
+    from . import _lib
+
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    pa = np.empty(c.shape[0], dtype=np.float64)
+    pb = np.empty(c.shape[0], dtype=np.float64)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    _lib.check(_lib.lib().mr_asym_tables(float(alpha), int(c.shape[0]), p(c), p(pa), p(pb)), "mr_asym_tables")
+    return pa, pb
+
+
+def asym_item_model(ds: Dataset, alpha: float, q: int, song_lo: int = 0, song_hi=None, users=None) -> np.ndarray:
+    """The asymmetric-cosine, locality-q item-based model as float64 rows
+    n_test x (song_hi - song_lo) (`users`: only those test users' rows, in the
+    given order): score(u, s) = the left fold from +0.0, over s2 in T(u) in
+    ascending song id, of t = w^q (q - 1 multiplications), w = C(s, s2) /
+    (pow_a[s] * pow_b[s2]) with C the distinct train users who heard both
+    (from the train CSR), the tables those of mr_asym_tables over song_count,
+    0.0 for a zero denominator; NaN for s in T(u). A Python loop over T(u) with
+    vector operations over s: the IEEE operation sequence of
+    mr_ibm_asym_device, which it is compared against bit for bit. At alpha =
+    0.5, q = 1 this is the reference's ItemBasedModel summed literally."""
+    song_hi = ds.n_songs if song_hi is None else int(song_hi)
+    song_lo, q = int(song_lo), int(q)
+    if not 0 <= song_lo <= song_hi <= ds.n_songs:
+        raise ValueError("asym_item_model: bad song range")
+    if not 1 <= q <= 8:
+        raise ValueError("asym_item_model: q must be in [1, 8]")
+    pow_a, pow_b = asym_tables(alpha, ds.song_count)
+    pa = pow_a[song_lo:song_hi]
+    tr_off = np.asarray(ds.tr_off, dtype=np.int64)
+    tr_songs = np.asarray(ds.tr_songs, dtype=np.int64)
+    deg = np.diff(tr_off)
+    order = np.argsort(tr_songs, kind="stable")                      # song -> train listeners
+    listeners = np.repeat(np.arange(ds.n_train, dtype=np.int64), deg)[order]
+    l_off = np.concatenate([[0], np.cumsum(np.bincount(tr_songs, minlength=ds.n_songs))])
+    width = song_hi - song_lo
+    terms = {}
+
+    def term(s2: int) -> np.ndarray:
+        if s2 not in terms:
+            L = listeners[l_off[s2]:l_off[s2 + 1]]                   # L_tr(s2)
+            n = deg[L]
+            idx = np.repeat(tr_off[L] - (np.cumsum(n) - n), n) + np.arange(int(n.sum()))
+            heard = tr_songs[idx]                                     # every listener's distinct songs
+            heard = heard[(heard >= song_lo) & (heard < song_hi)] - song_lo
+            num = np.bincount(heard, minlength=width).astype(np.float64)   # C(s, s2)
+            den = pa * pow_b[s2]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                w = np.where(den != 0, num / den, 0.0)
+            t = w
+            for _ in range(q - 1):
+                t = t * w
+            terms[s2] = t
+        return terms[s2]
+
+    rows = range(ds.n_test) if users is None else [int(u) for u in users]
+    out = np.empty((len(rows), width), dtype=np.float64)
+    for r, u in enumerate(rows):
+        mine = np.asarray(ds.te_songs[ds.te_off[u]:ds.te_off[u + 1]], dtype=np.int64)
+        acc = np.zeros(width, dtype=np.float64)
+        for s2 in np.sort(mine).tolist():                            # the fold order
+            acc = acc + term(s2)
+        acc[mine[(mine >= song_lo) & (mine < song_hi)] - song_lo] = np.nan
+        out[r] = acc
     return out
 
 

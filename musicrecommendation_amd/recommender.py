@@ -97,6 +97,29 @@ class MusicRecommender:
     def getItemBasedModelP(self) -> Model:
         return self.getItemBasedModel()
 
+    def getAsymmetricItemBasedModel(self, alpha: float, q: int) -> Model:
+        """The item-based model with the asymmetric cosine C / (c(s)^alpha *
+        c(s2)^(1-alpha)) raised to the locality exponent q before the sum over
+        T(u) (DeviceEnsemble.item_based), in getItemBasedModel's shape; alpha =
+        0.5, q = 1 is getItemBasedModel's model summed literally in fp64."""
+        from .ensemble import DeviceEnsemble
+
+        t = DeviceEnsemble(self.engine()).item_based(alpha, q)
+        return self._to_model(t.cpu().numpy())
+
+    def sweepItemSimilarity(self, alphas, qs, k: int = 500) -> List[Tuple[float, int, float]]:
+        """[(alpha, q, mAP@k)] over the grid alphas x qs (alpha-major): per
+        grid point one device model (DeviceEnsemble.item_based) ranked and
+        scored on the device (map_at); nothing is materialised on the host."""
+        from .ensemble import DeviceEnsemble
+
+        ens = DeviceEnsemble(self.engine())
+        out = []
+        for a in [float(x) for x in alphas]:
+            for q in [int(x) for x in qs]:
+                out.append((a, q, ens.map_at(ens.item_based(a, q), int(k))))
+        return out
+
     @staticmethod
     def sorted_model(model: Model) -> Model:
         """main.scala:57-59 ordering: (user, song, -score)."""
