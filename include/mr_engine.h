@@ -159,7 +159,12 @@ int mr_launch_info(const mr_ctx* ctx, int32_t* shape, int32_t* block_songs, int3
 /* Test-user batch of the separate / wide shapes (mr_run launches the stage-1 and
  * scoring kernels once per batch of *batch users, sized so the neighbour lists
  * fit 8 GiB; = n_test_users for the other shapes) and the stage-1 chunking of
- * the train users (*n_chunks chunks of *chunk users). */
+ * the train users (*n_chunks chunks of *chunk users). Diagnostic settings in
+ * the environment, for tests of the loops' later iterations (unset or invalid:
+ * no effect): MR_BATCH_USERS=n (n >= 1, read by mr_load) caps *batch of the
+ * separate / wide shapes at n; MR_LAUNCH_ROWS=n (n >= 8, read by every call
+ * that launches) caps the grid rows of one launch, wherever a call is split at
+ * the grid-row limit, at n rounded down to a multiple of 8. */
 int mr_batch_info(const mr_ctx* ctx, int32_t* batch, int32_t* chunk, int32_t* n_chunks);
 
 /* ItemBasedModel route chosen by mr_load (mr_options.ibm_route): *route = 1

@@ -262,8 +262,9 @@ int mr_ibm_asym_device(mr_ctx* ctx, double alpha, int32_t q, void* dense_dev) {
   if (const char* e = std::getenv("MR_ASYM_SUB")) cap = std::min(kAsymMaxSub, std::max(64, std::atoi(e)));
   const int sub = std::min(s.block_songs, cap);
   const int n_sub = (s.block_songs + sub - 1) / sub;
-  for (int u0 = 0; u0 < t.n_te; u0 += kAsymMaxBatch) {
-    const int nb = std::min(kAsymMaxBatch, t.n_te - u0);
+  const int rows = mr_internal::launch_rows(kAsymMaxBatch);  // (MR_LAUNCH_ROWS, diagnostic: fewer users per launch)
+  for (int u0 = 0; u0 < t.n_te; u0 += rows) {
+    const int nb = std::min(rows, t.n_te - u0);
     AsymParams ap{s.n_tr,  s.song_lo,   s.song_hi, s.block_songs, sub,        n_sub,      q,     t.f64, u0,
                   s.trs_off, s.trs_users, s.toff,    s.tsongs,      t.te_off,   t.te_songs, d_a.p, d_b.p, dense_dev};
     hipLaunchKernelGGL(k_asym_score, dim3(s.n_tiles * n_sub, nb), dim3(kAsymThreads), 0, st, ap);

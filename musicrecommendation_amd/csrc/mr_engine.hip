@@ -4218,6 +4218,22 @@ bool cooc_pays(double v_est, double e_est, const std::vector<int64_t>& bound, co
   return build + 0.49e-12 * e_est < 5.75e-12 * v_est;
 }
 
+// Diagnostic caps on the host loops that cut a run into pieces, so that tests
+// reach their second and later iterations with a few dozen test users (unset,
+// unparsable or out of range: production behaviour).
+// MR_BATCH_USERS=n (n >= 1, read at each mr_load): at most n test users per
+// two-hop batch of the separate / wide shapes (LaunchPlan.batch, what
+// mr_batch_info reports; the fused shape keeps n_test_users).
+// MR_LAUNCH_ROWS=n (n >= 8, read at each call that launches): at most n rounded
+// down to a multiple of 8 grid rows per launch wherever a loop splits at the
+// grid-row limit (mr_internal::launch_rows); the multiple of 8 keeps the XCD
+// remap's padding, as the production limit 65528 does.
+int batch_users_opt() {
+  const char* e = std::getenv("MR_BATCH_USERS");
+  const int n = e ? std::atoi(e) : 0;
+  return n >= 1 ? n : 0;  // 0: no cap
+}
+
 int wide_map_opt() {
   static const int m = [] {
     const char* e = std::getenv("MR_WIDE_MAP");
@@ -4514,6 +4530,7 @@ int plan_launch(const mr_options& opt, int n_tr, int n_te, int n_s, size_t free_
                         (size_t)std::max(1, dev_share);
   p.batch = fused ? n_te
                   : (int)std::max<size_t>(1, std::min<size_t>(std::min(n_te, 65528), budget / ((size_t)p.cap * 12)));
+  if (const int cap_users = fused ? 0 : batch_users_opt()) p.batch = std::min(p.batch, cap_users);
   return MR_OK;
 }
 
@@ -5556,8 +5573,9 @@ int run_cooc(mr_ctx* c) {
       }
   }
   if (timed) MR_HIP(hipEventRecord(ev[1], st));
-  for (int y0 = 0; y0 < c->n_te; y0 += 65528) {
-    const int ny = std::min(65528, c->n_te - y0);
+  const int rows = mr_internal::launch_rows(65528);
+  for (int y0 = 0; y0 < c->n_te; y0 += rows) {
+    const int ny = std::min(rows, c->n_te - y0);
     const int remap = wide_map_opt();
     ScoreParams sp{};
     sp.chunk = c->chunk; sp.n_chunks = c->n_chunks;
@@ -5615,6 +5633,8 @@ int run_model(mr_ctx* c, int model) {
   hipStream_t st = c->stream;
   const bool timed = c->opt.time_kernels != 0;
   const int k = c->opt.topk;
+  // rows per launch: stage 1 (plain grid), scoring (grid padded to 8 users under the XCD remap)
+  const int rows1 = mr_internal::launch_rows(65535), rows = mr_internal::launch_rows(65528);
   for (int user0 = 0; user0 < c->n_te; user0 += c->batch) {
     const int nb = std::min(c->batch, c->n_te - user0);
     hipEvent_t* ev = nullptr;
@@ -5635,20 +5655,20 @@ int run_model(mr_ctx* c, int model) {
       NbrParams np{c->n_tr, user0, c->cap, c->opt.frac_bits, c->chunk, c->n_chunks, c->te_off.p, c->te_songs.p,
                    c->trs_off.p, c->trs_users.p, c->q_song.p, c->sqrt_tr.p, c->sqrt_te.p, c->nbr_v.p, c->nbr_q.p,
                    c->nbr_cnt.p, c->n_chunks > 1 ? c->sbound.p : nullptr};
-      for (int y0 = 0; y0 < nb; y0 += 65535) {
+      for (int y0 = 0; y0 < nb; y0 += rows1) {
         NbrParams q = np;
         q.user0 = user0 + y0;
         q.nbr_v += (size_t)y0 * c->cap;
         q.nbr_q += (size_t)y0 * c->cap;
         q.nbr_cnt += (size_t)y0 * c->n_chunks;
-        hipLaunchKernelGGL(c->nbr_kernel[model], dim3(c->n_chunks, std::min(65535, nb - y0)), dim3(kThreads),
+        hipLaunchKernelGGL(c->nbr_kernel[model], dim3(c->n_chunks, std::min(rows1, nb - y0)), dim3(kThreads),
                            c->nbr_lds, st, q);
       }
       MR_HIP(hipGetLastError());
     }
     if (timed) MR_HIP(hipEventRecord(ev[1], st));
-    for (int y0 = 0; y0 < nb; y0 += 65528) {
-      const int ny = std::min(65528, nb - y0);
+    for (int y0 = 0; y0 < nb; y0 += rows) {
+      const int ny = std::min(rows, nb - y0);
       // separate shape: all tiles of a user on one XCD (grid padded to 8 users)
       const bool wide = c->shape == kShapeWide;
       int remap = (c->shape == kShapeSeparate && c->n_tiles > 1) || wide;
@@ -5781,14 +5801,15 @@ int launch_merge(mr_ctx* c, int32_t n_shards, int32_t n_te, int32_t k, const Mer
   const int lds = merge_lds_bytes(k);
   if (lds > 160 * 1024) return fail(MR_E_INVALID, "merge of %d lists x %d needs too much LDS", n_shards, k);
   MR_HIP(hipFuncSetAttribute((const void*)k_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  for (int y0 = 0; y0 < n_te; y0 += 65535) {
+  const int rows = launch_rows(65535);
+  for (int y0 = 0; y0 < n_te; y0 += rows) {
     MergeParams q = mp;
     q.keys += (size_t)y0 * k;
     q.songs += (size_t)y0 * k;
     q.out_keys += (size_t)y0 * k;
     q.out_songs += (size_t)y0 * k;
     if (q.out_scores) q.out_scores += (size_t)y0 * k;
-    hipLaunchKernelGGL(k_topk_merge, dim3(std::min(65535, n_te - y0)), dim3(kThreads), lds, c->stream, q);
+    hipLaunchKernelGGL(k_topk_merge, dim3(std::min(rows, n_te - y0)), dim3(kThreads), lds, c->stream, q);
   }
   MR_HIP(hipGetLastError());
   return MR_OK;
@@ -5830,6 +5851,12 @@ int topk_records(mr_ctx* c, void** records, int64_t* rec_bytes) {
 }
 
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
+int launch_rows(int production_max) {
+  const char* e = std::getenv("MR_LAUNCH_ROWS");
+  const int n = e ? std::atoi(e) : 0;
+  return n >= 8 ? std::min(production_max, n / 8 * 8) : production_max;
+}
 
 int similar_tables(mr_ctx* c, SimilarTables* out) {
   if (!c || !out) return fail(MR_E_INVALID, "null argument");
@@ -6144,10 +6171,11 @@ int mr_topk_dense_device(mr_ctx* c, const void* dense_dev, int32_t k) {
   MR_HIP(hipSetDevice(c->opt.device));
   MR_HIP(hipMemsetAsync(c->flag.p, 0, sizeof(unsigned), c->stream));
   const bool f64 = c->opt.out_dtype == MR_OUT_F64;
-  for (int y0 = 0; y0 < c->n_te; y0 += 65535) {
+  const int rows = mr_internal::launch_rows(65535);
+  for (int y0 = 0; y0 < c->n_te; y0 += rows) {
     DenseTopkParams tp{y0, c->width, c->song_lo, k, dense_dev, c->top_key.p, c->top_song.p, c->top_score.p,
                        c->flag.p};
-    const int ny = std::min(65535, c->n_te - y0);
+    const int ny = std::min(rows, c->n_te - y0);
     if (f64) hipLaunchKernelGGL(k_topk_dense<double>, dim3(ny), dim3(kWideThreads), 0, c->stream, tp);
     else hipLaunchKernelGGL(k_topk_dense<float>, dim3(ny), dim3(kWideThreads), 0, c->stream, tp);
     MR_HIP(hipGetLastError());

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "mr_engine.h"
+#include "mr_internal.h"
 
 namespace mr_host {
 int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
@@ -1022,9 +1023,10 @@ int mr_combine_device(mr_ctx* ctx, int kind, double param, uint64_t seed, int64_
                 (long long)pair_base, (long long)(param * (double)n_pairs),  // (p * length).toInt, MR:371
                 reinterpret_cast<const long long*>(v.te_off), v.te_songs, ubm, ibm, out};
   hipStream_t st = (hipStream_t)v.stream;
-  for (int y0 = 0; y0 < v.n_test_users; y0 += 65535) {
+  const int rows = mr_internal::launch_rows(65535);
+  for (int y0 = 0; y0 < v.n_test_users; y0 += rows) {
     CombParams q = cp;
-    const int ny = std::min(65535, v.n_test_users - y0);
+    const int ny = std::min(rows, v.n_test_users - y0);
     const size_t esz = v.out_dtype == MR_OUT_F64 ? 8 : 4;
     q.n_te = ny;
     q.te_off = cp.te_off + y0;  // values index the whole te_songs: pairs before user y0 + u are
@@ -1071,9 +1073,10 @@ int mr_combine_all_device(mr_ctx* ctx, double alpha, double ibm_percentage, doub
     MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part.p), (size_t)nblk * 6 * sizeof(double), st));
     MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part2.p), (size_t)kRed * 6 * sizeof(double), st));
   }
-  for (int y0 = 0; gx > 0 && y0 < v.n_test_users; y0 += 65535) {
+  const int rows = mr_internal::launch_rows(65535);
+  for (int y0 = 0; gx > 0 && y0 < v.n_test_users; y0 += rows) {
     Comb3Params q = cp;
-    const int ny = std::min(65535, v.n_test_users - y0);
+    const int ny = std::min(rows, v.n_test_users - y0);
     q.n_te = ny;
     q.te_off = cp.te_off + y0;  // values index the whole te_songs (see mr_combine_device)
     q.pair_base = cp.pair_base + (long long)y0 * v.n_songs;

@@ -72,6 +72,14 @@ int asym_tables(mr_ctx* c, AsymTables* out);
 int rank_rows_async(void* stream, int f64, int32_t n_rows, int32_t width, int32_t song_lo, const void* dense,
                     int32_t K, int32_t* songs, double* scores);
 
+// Rows (grid y: test users or queries) of one launch of every host loop that
+// splits a call at the grid-row limit: production_max (65535, or 65528 where
+// the XCD remap pads the grid to a multiple of 8 rows), unless
+// MR_LAUNCH_ROWS=n (diagnostic, n >= 8, read at each call) lowers it to n
+// rounded down to a multiple of 8, so that a few dozen rows take the second
+// and later iterations. Never below 8; any other value is ignored.
+int launch_rows(int production_max);
+
 // Set the calling thread's mr_last_error() message; returns code.
 int set_error(int code, const char* msg);
 

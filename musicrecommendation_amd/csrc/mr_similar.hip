@@ -183,9 +183,11 @@ int mr_similar_songs_device(mr_ctx* ctx, int32_t n_q, const int32_t* query_songs
 
   MR_HIP(hipSetDevice(t.device));
   hipStream_t st = (hipStream_t)t.stream;
-  // queries per launch: the lists' scratch rows stay within MR_SIMILAR_SCRATCH_BYTES (one row at least)
+  // queries per launch: the lists' scratch rows stay within MR_SIMILAR_SCRATCH_BYTES (one row at least;
+  // MR_LAUNCH_ROWS, diagnostic: fewer queries per launch)
   const int per = (int)std::max<int64_t>(
-      1, std::min<int64_t>(std::min(n_q, kSimMaxBatch), (int64_t)MR_SIMILAR_SCRATCH_BYTES / (8 * (int64_t)width)));
+      1, std::min<int64_t>(std::min(n_q, mr_internal::launch_rows(kSimMaxBatch)),
+                           (int64_t)MR_SIMILAR_SCRATCH_BYTES / (8 * (int64_t)width)));
   Tmp<int> d_q;
   Tmp<double> d_listed;
   d_q.st = d_listed.st = st;
