@@ -599,6 +599,65 @@ int mr_similar_songs_device(mr_ctx* ctx, int32_t n_q, const int32_t* query_songs
 int mr_asym_tables(double alpha, int32_t n, const int32_t* counts, double* pow_a, double* pow_b); /* host only */
 int mr_ibm_asym_device(mr_ctx* ctx, double alpha, int32_t q, void* dense_dev);
 
+/* ---- asymmetric-cosine, locality-q user-based model ----------------------------
+ * The other half of the same neighbourhood method: the UserBasedModel
+ * (MR:140-166) with the asymmetry exponent alpha in [0, 1] and the locality
+ * exponent q in [1, MR_ASYM_MAX_Q] on the user-user similarity. It is defined
+ * the way mr_run's MR_UBM is — per-neighbour weights computed in fp64,
+ * quantised once to fixed point, summed in int64 — so the sum has no order.
+ * mr_ubm_asym_device: for every test user u of the context and every song s
+ *   of its shard [song_lo, song_hi)
+ *   Tables:   pa[u] = pow_a of mr_asym_tables(alpha, n_te, te_len, ...) =
+ *     te_len[u]^alpha, pb[v] = pow_b of mr_asym_tables(alpha, n_tr, tr_len, ...)
+ *     = tr_len[v]^(1-alpha), the lengths mr_dataset's (duplicates counted,
+ *     MR:147), with that call's three exact cases: alpha = 0.5 gives the
+ *     scoring's own sqrt values on both sides. alpha is the ACTIVE (test)
+ *     user's share: w = |u ∩ v| / (|u|^alpha * |v|^(1-alpha)).
+ *   Overlap:  y(u, v) = |T(u) ∩ S(v)|, distinct songs (MR_UBM's stage-1 count).
+ *   Weight:   for y >= 1, w = (double)y / (pa[u] * pb[v]), 0.0 for a zero
+ *     denominator; t = w, then q - 1 times t = t * w; key(u, v) =
+ *     (int64)rint(t * 2^F), round-half-even (fp64, no pow, no contraction).
+ *     y = 0 gives key 0. A term below 2^-(F+1) rounds to key 0 and vanishes:
+ *     that is the model's resolution, and why F is an argument (large q
+ *     makes small weights; F = 52 keeps what F = 32 drops).
+ *   Score:    acc(u, s) = the int64 sum of key(u, v) over v in L_tr(s), the
+ *     train listeners of s; score = (double)acc * 2^-F; NaN for s in T(u).
+ *   frac_bits: F; 0 means the context's mr_options.frac_bits, otherwise it must
+ *     be in [8, 52]. Headroom rule: F + ceil(log2(max_s c_tr(s) + 1)) <= 62,
+ *     max_s c_tr(s) the largest train-listener count of any song of the
+ *     dataset (w <= 1 up to rounding since y <= min(te_len[u], tr_len[v]), so
+ *     key <= about 2^F and acc stays inside int64); otherwise MR_E_INVALID.
+ *   dense_dev: caller-owned DEVICE buffer of n_te x (song_hi - song_lo)
+ *     elements of the context's out_dtype (f32: the fp64 score rounded once).
+ *   Every argument is checked before any launch, in this order: MR_E_INVALID
+ *     for a NULL ctx, alpha outside [0, 1] or NaN, q outside
+ *     [1, MR_ASYM_MAX_Q], frac_bits not 0 and outside [8, 52], a NULL
+ *     dense_dev; MR_E_STATE before mr_load; MR_E_INVALID for the headroom rule
+ *     (no output is written on any error). n_te = 0 or an empty shard succeeds
+ *     without a launch. Synchronous on the context stream.
+ *   The result is a pure function of the loaded dataset, alpha, q, F and the
+ *     columns the shard holds: it does not depend on the launch shape,
+ *     block_songs, train_order (the renumbering of train users), ibm_route,
+ *     stage1_chunk, the chunking of train users, the batching of test users or
+ *     the sub-range size. Song shards concatenate by column. At alpha = 0.5,
+ *     q = 1, frac_bits = 0 an f64 context's result is bit-equal to the dense
+ *     model of mr_run(MR_UBM).
+ *   mr_load keeps host copies of te_len, tr_len (in the context's train order)
+ *     and max_s c_tr(s) (4 * (n_tr + n_te) bytes) and uploads nothing for this
+ *     call; each call uploads its two tables (8 * (n_te + n_tr) bytes) into
+ *     stream-ordered scratch. Two kernels (csrc/mr_uasym.hip): the weights of
+ *     one (train-user chunk, test user) per workgroup into compacted (v, key)
+ *     lists in per-call scratch, then one 1024-thread workgroup per (song
+ *     sub-range of at most 8192 songs, test user) that adds every neighbour's
+ *     key along its train row. Test users run in batches whose scratch
+ *     (12 * n_tr bytes and 4 bytes per chunk, per user) fits
+ *     MR_UASYM_SCRATCH_BYTES, at least one user. In the environment
+ *     (diagnostic; results identical): MR_UASYM_CHUNK=n (16..8192) train users
+ *     per chunk, MR_UASYM_BATCH=n (>= 1) test users per batch, MR_UASYM_SUB=n
+ *     (64..8192) songs per sub-range; MR_LAUNCH_ROWS as everywhere. */
+#define MR_UASYM_SCRATCH_BYTES (256 << 20)
+int mr_ubm_asym_device(mr_ctx* ctx, double alpha, int32_t q, int32_t frac_bits, void* dense_dev);
+
 /* Kernel timing of mr_run calls made with opt.time_kernels = 1: per kernel
  * (0 = separate stage-1 kernel — neighbour lists —, 1 = the
  * scoring kernels — stage 2, fused stage 1, the in-launch top-k merge, the wide

@@ -201,6 +201,7 @@ SIGNATURES = {
     "mr_similar_songs_device": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "mr_asym_tables": (c_int, [c_double, c_int32, c_void_p, c_void_p, c_void_p]),
     "mr_ibm_asym_device": (c_int, [c_void_p, c_double, c_int32, c_void_p]),
+    "mr_ubm_asym_device": (c_int, [c_void_p, c_double, c_int32, c_int32, c_void_p]),
     "mr_last_error": (c_char_p, []),
     "mr_corpus_from_tsv": (c_int, [c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
     "mr_corpus_dataset": (c_int, [c_void_p, POINTER(MrDataset)]),

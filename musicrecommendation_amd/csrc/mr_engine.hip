@@ -3958,6 +3958,10 @@ struct mr_ctx {
   DevBuf<double> sqrt_c, sqrt_tr, sqrt_te, top_score;
   DevBuf<float> rsq_c;  // wide shape: 1 / sqrt(c(s)) as fp32 (wide_cand_topk's approximations)
   std::vector<int32_t> song_count;  // host copy of mr_dataset.song_count (mr_ibm_asym_device's tables)
+  // host copies for mr_ubm_asym_device's tables: te_len, tr_len in the context's train order
+  // (TrainIndex::len) and the largest train-listener count of any song
+  std::vector<int32_t> te_len_h, tr_len_h;
+  int32_t max_ctr = 0;
   bool cand_on = false; // wide shape, top-k only: the candidate-only tile top-k (MR_WIDE_CAND=0: off)
   DevBuf<unsigned char> dense;
   DevBuf<long long> stamps;
@@ -4017,6 +4021,7 @@ struct mr_ctx {
     sqrt_c.release(); sqrt_tr.release(); sqrt_te.release(); top_score.release();
     rsq_c.release(); cand_on = false;
     song_count = std::vector<int32_t>();
+    te_len_h = std::vector<int32_t>(); tr_len_h = std::vector<int32_t>(); max_ctr = 0;
     dense.release();
     mm_key.release(); mm_on = mm_valid = false;
     stamps.release();
@@ -5319,6 +5324,9 @@ int mr_load(mr_ctx* c, const mr_dataset* d) {
   c->cap = lp.cap; c->batch = lp.batch;
   c->chunk = lp.chunk; c->n_chunks = lp.n_chunks;
   c->song_count.assign(d->song_count, d->song_count + n_s);
+  c->te_len_h.assign(d->te_len, d->te_len + n_te);
+  c->tr_len_h.assign(ti.len.begin(), ti.len.begin() + n_tr);
+  c->max_ctr = col_tr.empty() ? 0 : *std::max_element(col_tr.begin(), col_tr.end());
   c->loaded = true;
   c->ran = false;
   return MR_OK;
@@ -5876,6 +5884,18 @@ int asym_tables(mr_ctx* c, AsymTables* out) {
   out->te_off = c->te_off.p;
   out->te_songs = c->te_songs.p;
   out->song_count = c->song_count.data();
+  return MR_OK;
+}
+
+int uasym_tables(mr_ctx* c, UasymTables* out) {
+  if (!c || !out) return fail(MR_E_INVALID, "null argument");
+  if (!c->loaded) return fail(MR_E_STATE, "asymmetric user-based model before mr_load");
+  int rc = asym_tables(c, &out->asym);
+  if (rc) return rc;
+  out->te_len = c->te_len_h.data();
+  out->tr_len = c->tr_len_h.data();
+  out->max_ctr = c->max_ctr;
+  out->frac_bits = c->opt.frac_bits;
   return MR_OK;
 }
 

@@ -65,6 +65,21 @@ struct AsymTables {
 };
 int asym_tables(mr_ctx* c, AsymTables* out);
 
+// The same tables plus what the asymmetric user-based model reads
+// (csrc/mr_uasym.hip): the HOST copies mr_load keeps of mr_dataset.te_len, of
+// tr_len in the context's internal train order (the ids trs_users and toff are
+// indexed by) and of the largest train-listener count of any song
+// (4 * (n_tr + n_te) bytes), and the context's mr_options.frac_bits. Valid
+// until mr_load / mr_destroy. MR_E_STATE before mr_load.
+struct UasymTables {
+  AsymTables asym;
+  const int32_t* te_len;  // host: |T(u)| with duplicates [n_te]
+  const int32_t* tr_len;  // host: |S(v)| with duplicates [n_tr], v the context's train id
+  int32_t max_ctr;        // max over every song s of c_tr(s) = |L_tr(s)|
+  int frac_bits;          // mr_options.frac_bits of the context
+};
+int uasym_tables(mr_ctx* c, UasymTables* out);
+
 // k_rank_dense over n_rows rows of `width` values (f64 != 0: double, else
 // float; NaN = no entry) into songs / scores [n_rows][K] (scores may be NULL),
 // song id = song_lo + column: enqueued on `stream` (a hipStream_t), no host

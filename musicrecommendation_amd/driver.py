@@ -4,6 +4,7 @@ MN:8-123, src/main/scala/distributed.scala DS:55-602) on the MI355X engine.
     python -m musicrecommendation_amd.driver TRAIN_N TEST_N [--resources DIR]
         [--devices 0,1,...] [--song-shards G_s] [--user-blocks G_u] [--distributed] [--quiet]
         [--sweep KIND:LO:HI:N ...] [--recommend K[:PATH]] [--similar K[:PATH]] [--asym ALPHA:Q]
+        [--asym-user ALPHA:Q[:F]]
 
 Same flow and output as main.scala: load train_{N}_{M}.txt, test_{N}_{M}.txt,
 test_labels_{N}_{M}.txt (MN:21-23), build the recommender (untimed, MN:27),
@@ -50,6 +51,12 @@ asymmetricItemBasedModel: the item-based model with the similarity C /
 (c(s)^ALPHA * c(s2)^(1-ALPHA)) raised to the power Q before the sum over T(u)
 (DeviceEnsemble.item_based; 0.5:1 is the reference's model summed in fp64),
 timed, evaluated and, with --recommend, ranked like the others.
+
+--asym-user ALPHA:Q[:F] (ALPHA in [0, 1], Q in 1..8, F in 8..52, default: the
+engine's 32) adds asymmetricUserBasedModel in the same way: the user-based model
+with the neighbour weight |T(u) ∩ S(v)| / (|u|^ALPHA * |v|^(1-ALPHA)) raised to
+the power Q, in fixed point with F fraction bits (DeviceEnsemble.user_based;
+0.5:1 is the user-based model bit for bit). Both flags may be given.
 """
 from __future__ import annotations
 
@@ -158,6 +165,30 @@ def parse_asym(spec) -> Tuple[float, int]:
     return a, q
 
 
+def parse_asym_user(spec) -> Tuple[float, int, Optional[int]]:
+    """--asym-user ALPHA:Q[:F] (or (alpha, q) / (alpha, q, F)) -> (alpha, q, F
+    or None for the engine's); ValueError on a bad spec."""
+    if isinstance(spec, (tuple, list)):
+        parts = list(spec)
+    else:
+        parts = str(spec).split(":")
+    if len(parts) not in (2, 3):
+        raise ValueError(f"--asym-user {spec!r}: expected ALPHA:Q[:F]")
+    try:
+        a, q = parse_asym(tuple(parts[:2]))
+    except ValueError as e:  # the same checks, named for this flag
+        raise ValueError(f"--asym-user {spec!r}: {str(e).rsplit(': ', 1)[-1]}") from None
+    f = None
+    if len(parts) == 3 and parts[2] is not None:
+        try:
+            f = int(parts[2])
+        except (TypeError, ValueError):
+            raise ValueError(f"--asym-user {spec!r}: F is an integer") from None
+        if not 8 <= f <= 52:
+            raise ValueError(f"--asym-user {spec!r}: F must be in [8, 52]")
+    return a, q, f
+
+
 def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
     """N evenly spaced values LO + i*(HI-LO)/(N-1) (N = 1: LO alone)."""
     return [lo + i * (hi - lo) / (n - 1) for i in range(n)] if n > 1 else [lo]
@@ -166,7 +197,7 @@ def sweep_grid(lo: float, hi: float, n: int) -> List[float]:
 def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[int]] = None,
         song_shards: Optional[int] = None, user_blocks: int = 1, verbose: bool = True, seed: int = 1,
         distributed: bool = False, sweeps: Optional[Sequence[str]] = None, recommend=None, similar=None,
-        asym=None) -> dict:
+        asym=None, asym_user=None) -> dict:
     import numpy as np
 
     from .dataset import Dataset
@@ -177,6 +208,7 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
     rec = parse_recommend(recommend) if recommend is not None else None
     sim = parse_similar(similar) if similar is not None else None
     asy = parse_asym(asym) if asym is not None else None
+    uasy = parse_asym_user(asym_user) if asym_user is not None else None
 
     n_thr = 11 if distributed else 10  # DS:395 vs MR:590
     if song_shards is None:  # one song shard per listed GPU and user block (DS:477-479's song partition)
@@ -222,6 +254,10 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
         models.append(("asymmetricItemBasedModel",
                        timed(lambda: ens.item_based(*asy), f"asymmetricItemBasedModel (alpha {asy[0]}, q {asy[1]})",
                              verbose)))
+    if uasy is not None:
+        models.append(("asymmetricUserBasedModel",
+                       timed(lambda: ens.user_based(*uasy),
+                             f"asymmetricUserBasedModel (alpha {uasy[0]}, q {uasy[1]})", verbose)))
     maps = {}
     for name, t in models:
         maps[name] = timed(lambda: ens.threshold_map(t, n_thresholds=n_thr), f"{name} model mAP", verbose)  # MN:101-110
@@ -278,6 +314,8 @@ def run(train_n: int, test_n: int, resources: str, devices: Optional[Sequence[in
         out["recommend"] = {"K": rec[0], "path": rec[1]}
     if asy is not None:
         out["asym"] = {"alpha": asy[0], "q": asy[1]}
+    if uasy is not None:
+        out["asym_user"] = {"alpha": uasy[0], "q": uasy[1], "frac_bits": uasy[2]}
     if sim is not None:
         out["similar"] = {"K": sim[0], "path": sim[1], "queries": n_sim}
     return out
@@ -311,6 +349,13 @@ def _asym_arg(spec: str) -> Tuple[float, int]:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _asym_user_arg(spec: str) -> Tuple[float, int, Optional[int]]:
+    try:
+        return parse_asym_user(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("train_n", type=int, nargs="?", default=None)  # MN:15 default 100 (DS:61: 300)
@@ -336,11 +381,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--asym", default=None, metavar="ALPHA:Q", type=_asym_arg,
                     help="add the asymmetric-cosine (ALPHA in [0, 1]), locality-Q (1..8) item-based model to the run "
                          "as asymmetricItemBasedModel")
+    ap.add_argument("--asym-user", default=None, metavar="ALPHA:Q[:F]", type=_asym_user_arg,
+                    help="add the asymmetric-cosine (ALPHA in [0, 1]), locality-Q (1..8) user-based model with F "
+                         "fraction bits (8..52, default: the engine's) to the run as asymmetricUserBasedModel")
     a = ap.parse_args(argv)
     devices = [int(x) for x in a.devices.split(",") if x.strip()] if a.devices else None
     train_n = a.train_n if a.train_n is not None else (300 if a.distributed else 100)
     run(train_n, a.test_n, a.resources, devices, a.song_shards, a.user_blocks, verbose=not a.quiet, seed=a.seed,
-        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend, similar=a.similar, asym=a.asym)
+        distributed=a.distributed, sweeps=a.sweep, recommend=a.recommend, similar=a.similar, asym=a.asym,
+        asym_user=a.asym_user)
     return 0
 
 

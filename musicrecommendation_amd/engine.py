@@ -430,6 +430,18 @@ class Engine:
         _lib.check(self._L.mr_ibm_asym_device(self._h, float(alpha), int(q), ctypes.c_void_p(dense_ptr or None)),
                    "mr_ibm_asym_device")
 
+    # ---- asymmetric-cosine, locality-q user-based model (mr_ubm_asym_device) -----
+    def ubm_asym(self, alpha: float, q: int, dense_ptr: int, frac_bits: int = 0) -> None:
+        """The user-based model with neighbour weight (|T(u) ∩ S(v)| /
+        (te_len[u]^alpha * tr_len[v]^(1-alpha)))^q, quantised once to
+        frac_bits fraction bits (0: this context's) and summed in int64 over the
+        train listeners of every song, into a caller-owned device buffer (n_test
+        x width of this engine's dtype, NaN for heard songs); alpha = 0.5, q =
+        1, frac_bits = 0 is run("ubm")'s dense model bit for bit; synchronous
+        (mr_ubm_asym_device)."""
+        _lib.check(self._L.mr_ubm_asym_device(self._h, float(alpha), int(q), int(frac_bits),
+                                              ctypes.c_void_p(dense_ptr or None)), "mr_ubm_asym_device")
+
     def timing_begin(self) -> None:
         """Open a timing window (one event on the engine stream)."""
         _lib.check(self._L.mr_timing_begin(self._h), "mr_timing_begin")

@@ -34,6 +34,10 @@ item_based gives that similarity its two knobs, the asymmetry exponent alpha
 and the locality exponent q of the Million Song Dataset Challenge's
 neighbourhood method (csrc/mr_asym.hip); its result is a dense model like
 model("ibm").
+
+user_based gives the user-user similarity the same two knobs
+(csrc/mr_uasym.hip), in the engine's own fixed-point form: at the defaults it
+is model("ubm") bit for bit.
 """
 from __future__ import annotations
 
@@ -173,6 +177,21 @@ class DeviceEnsemble:
         t = self.empty()
         self._after_torch()
         self.e.ibm_asym(alpha, q, t.data_ptr())
+        return t
+
+    def user_based(self, alpha: float = 0.5, q: int = 1, frac_bits: Optional[int] = None):
+        """The asymmetric-cosine, locality-q user-based model into a new device
+        tensor (mr_ubm_asym_device, csrc/mr_uasym.hip): score(u, s) = the sum
+        over the train listeners v of s of (|T(u) ∩ S(v)| / (te_len[u]^alpha *
+        tr_len[v]^(1-alpha)))^q, every weight quantised once to frac_bits
+        fraction bits (None: the context's; else 8..52) and summed in int64,
+        so the result has no summation order; weights below 2^-(frac_bits+1)
+        vanish. The defaults are model("ubm") bit for bit on an f64 context. A
+        model like any other: rank, map_at, threshold_map and the combinations
+        accept it."""
+        t = self.empty()
+        self._after_torch()
+        self.e.ubm_asym(alpha, q, t.data_ptr(), 0 if frac_bits is None else int(frac_bits))
         return t
 
     def _combine(self, kind: int, ubm, ibm, param: float, seed: int = 0):

@@ -16,6 +16,9 @@
 * ``asym_item_model`` — the numpy restatement of the asymmetric-cosine,
   locality-q item-based model (mr_ibm_asym_device), tables from the library's
   host-only mr_asym_tables.
+* ``asym_user_keys`` / ``asym_user_model`` — the numpy restatement of the
+  asymmetric-cosine, locality-q user-based model (mr_ubm_asym_device):
+  fixed-point neighbour weights from the same tables, int64 sums.
 Vectorised over the dense n_test x n_songs score matrix (NaN = no pair).
 """
 from __future__ import annotations
@@ -257,6 +260,92 @@ def asym_item_model(ds: Dataset, alpha: float, q: int, song_lo: int = 0, song_hi
             acc = acc + term(s2)
         acc[mine[(mine >= song_lo) & (mine < song_hi)] - song_lo] = np.nan
         out[r] = acc
+    return out
+
+
+def _asym_user_check(q: int, frac_bits: int) -> None:
+    if not 1 <= q <= 8:
+        raise ValueError("asym_user_model: q must be in [1, 8]")
+    if not 8 <= frac_bits <= 52:
+        raise ValueError("asym_user_model: frac_bits must be in [8, 52]")
+
+
+def _train_listeners(ds: Dataset):
+    """(listeners, l_off): the song -> train users CSR of the train CSR."""
+    tr_songs = np.asarray(ds.tr_songs, dtype=np.int64)
+    deg = np.diff(np.asarray(ds.tr_off, dtype=np.int64))
+    order = np.argsort(tr_songs, kind="stable")
+    listeners = np.repeat(np.arange(ds.n_train, dtype=np.int64), deg)[order]
+    l_off = np.concatenate([[0], np.cumsum(np.bincount(tr_songs, minlength=ds.n_songs))]).astype(np.int64)
+    return listeners, l_off
+
+
+def asym_user_keys(ds: Dataset, alpha: float, q: int, frac_bits: int = 32, users=None) -> list:
+    """Per test user (`users`: only those, in the given order) the pair
+    (neighbours, keys): the train users v with y = |T(u) ∩ S(v)| >= 1,
+    ascending, and their fixed-point weights key = rint(t * 2^frac_bits) as
+    int64, t = w^q by q - 1 multiplications, w = y / (pa[u] * pb[v]) (0.0 for a
+    zero denominator), pa = te_len^alpha and pb = tr_len^(1-alpha) from
+    mr_asym_tables. A key of 0 is a neighbour whose weight is below
+    2^-(frac_bits+1): it adds nothing to any score."""
+    q, frac_bits = int(q), int(frac_bits)
+    _asym_user_check(q, frac_bits)
+    pa = asym_tables(alpha, ds.te_len)[0]
+    pb = asym_tables(alpha, ds.tr_len)[1]
+    listeners, l_off = _train_listeners(ds)
+    two_f = np.float64(2.0) ** frac_bits
+    out = []
+    for u in (range(ds.n_test) if users is None else [int(x) for x in users]):
+        mine = np.asarray(ds.te_songs[ds.te_off[u]:ds.te_off[u + 1]], dtype=np.int64)
+        parts = [listeners[l_off[s2]:l_off[s2 + 1]] for s2 in mine.tolist()]
+        heard_by = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        y = np.bincount(heard_by, minlength=ds.n_train)               # distinct songs: both sides are sets
+        nb = np.flatnonzero(y)
+        den = pa[u] * pb[nb]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            w = np.where(den != 0, y[nb].astype(np.float64) / den, 0.0)
+        t = w
+        for _ in range(q - 1):
+            t = t * w
+        out.append((nb, np.rint(t * two_f).astype(np.int64)))
+    return out
+
+
+def asym_user_model(ds: Dataset, alpha: float, q: int, frac_bits: int = 32, song_lo: int = 0, song_hi=None,
+                    users=None) -> np.ndarray:
+    """The asymmetric-cosine, locality-q user-based model as float64 rows
+    n_test x (song_hi - song_lo) (`users`: only those test users' rows, in the
+    given order): score(u, s) = (the int64 sum over the train listeners v of s
+    of key(u, v)) * 2^-frac_bits with asym_user_keys' keys; NaN for s in T(u).
+    Integer sums over the train CSR rows of u's neighbours (no dense train x
+    song matrix), so there is no summation order: the definition
+    mr_ubm_asym_device is compared against bit for bit. At alpha = 0.5, q = 1
+    this is the engine's fixed-point UserBasedModel (oracle.native.fp_model's
+    "ubm") bit for bit."""
+    song_hi = ds.n_songs if song_hi is None else int(song_hi)
+    song_lo = int(song_lo)
+    if not 0 <= song_lo <= song_hi <= ds.n_songs:
+        raise ValueError("asym_user_model: bad song range")
+    rows = list(range(ds.n_test)) if users is None else [int(u) for u in users]
+    keys = asym_user_keys(ds, alpha, q, frac_bits, users=rows)
+    tr_off = np.asarray(ds.tr_off, dtype=np.int64)
+    tr_songs = np.asarray(ds.tr_songs, dtype=np.int64)
+    deg = np.diff(tr_off)
+    width = song_hi - song_lo
+    inv_f = np.float64(2.0) ** -int(frac_bits)
+    out = np.empty((len(rows), width), dtype=np.float64)
+    for r, (u, (nb, key)) in enumerate(zip(rows, keys)):
+        n = deg[nb]
+        idx = np.repeat(tr_off[nb] - (np.cumsum(n) - n), n) + np.arange(int(n.sum()))
+        songs = tr_songs[idx]                                         # every neighbour's distinct songs
+        add = np.repeat(key, n)
+        keep = (songs >= song_lo) & (songs < song_hi)
+        acc = np.zeros(width, dtype=np.int64)
+        np.add.at(acc, songs[keep] - song_lo, add[keep])
+        row = acc.astype(np.float64) * inv_f
+        mine = np.asarray(ds.te_songs[ds.te_off[u]:ds.te_off[u + 1]], dtype=np.int64)
+        row[mine[(mine >= song_lo) & (mine < song_hi)] - song_lo] = np.nan
+        out[r] = row
     return out
 
 

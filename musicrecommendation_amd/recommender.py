@@ -120,6 +120,32 @@ class MusicRecommender:
                 out.append((a, q, ens.map_at(ens.item_based(a, q), int(k))))
         return out
 
+    def getAsymmetricUserBasedModel(self, alpha: float, q: int, frac_bits: Optional[int] = None) -> Model:
+        """The user-based model with the asymmetric cosine |T(u) ∩ S(v)| /
+        (|u|^alpha * |v|^(1-alpha)) raised to the locality exponent q, every
+        neighbour weight in fixed point with frac_bits fraction bits (None: the
+        engine's) and summed in int64 (DeviceEnsemble.user_based), in
+        getUserBasedModel's shape; alpha = 0.5, q = 1 is getUserBasedModel's
+        model bit for bit."""
+        from .ensemble import DeviceEnsemble
+
+        t = DeviceEnsemble(self.engine()).user_based(alpha, q, frac_bits)
+        return self._to_model(t.cpu().numpy())
+
+    def sweepUserSimilarity(self, alphas, qs, k: int = 500,
+                            frac_bits: Optional[int] = None) -> List[Tuple[float, int, float]]:
+        """[(alpha, q, mAP@k)] over the grid alphas x qs (alpha-major): per
+        grid point one device model (DeviceEnsemble.user_based) ranked and
+        scored on the device (map_at); nothing is materialised on the host."""
+        from .ensemble import DeviceEnsemble
+
+        ens = DeviceEnsemble(self.engine())
+        out = []
+        for a in [float(x) for x in alphas]:
+            for q in [int(x) for x in qs]:
+                out.append((a, q, ens.map_at(ens.user_based(a, q, frac_bits), int(k))))
+        return out
+
     @staticmethod
     def sorted_model(model: Model) -> Model:
         """main.scala:57-59 ordering: (user, song, -score)."""
