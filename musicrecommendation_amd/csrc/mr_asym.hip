@@ -11,9 +11,9 @@
 //   2. the fp64 accumulators live in registers: thread tid owns the songs
 //      tid + j * 1024 of the sub-range, j < kAsymAcc;
 //   3. for each s2 of T(u), ascending (te_off / te_songs): the workgroup walks
-//      the train listeners L_tr(s2) through the tile-major train CSR exactly as
-//      k_similar_count does (listener id -> toff pair -> segment ids, software-
-//      pipelined three levels deep, LDS adds without a returned value), then
+//      the train listeners L_tr(s2) through the tile-major train CSR with the
+//      shared walk_tile_lists (csrc/mr_tile_walk.h) in its 2-byte segment-load
+//      form, as k_similar_count does (LDS adds without a returned value), then
 //      after a barrier every thread folds t = w^q, w = (double)C / (pow_a[s] *
 //      pow_b[s2]), into its accumulators for its songs with C >= 1 and clears
 //      the counters it read (so the next s2 starts from zero), then a barrier;
@@ -28,34 +28,25 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <vector>
 
 #include "mr_engine.h"
+#include "mr_hip_util.h"
 #include "mr_internal.h"
-
-namespace mr_host {
-int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
-}
+#include "mr_tile_walk.h"
 
 namespace {
 
+using mr_hip::Drain;
+using mr_hip::Tmp;
 using mr_host::fail;
-
-#define MR_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(e_ == hipErrorOutOfMemory ? MR_E_OOM : MR_E_HIP, "%s failed: %s (%s:%d)", #call, \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-  } while (0)
 
 constexpr int kAsymThreads = 1024;
 constexpr int kAsymR = 2;          // listeners per thread and iteration
 constexpr int kAsymSeg = 4;        // segment ids loaded together
 constexpr int kAsymAcc = 8;        // fp64 accumulators per thread
 constexpr int kAsymMaxSub = kAsymThreads * kAsymAcc;  // songs per sub-range: 32 KiB of u32 counters
-constexpr int kAsymMaxBatch = 65535;                  // test users per launch (grid y)
+constexpr int kAsymMaxBatch = mr_internal::kGridRows;  // test users per launch (grid y)
 
 struct AsymParams {
   int n_tr, song_lo, song_hi, block_songs, sub, n_sub;  // sub: songs per sub-range, n_sub: sub-ranges per tile
@@ -76,25 +67,23 @@ __global__ __launch_bounds__(kAsymThreads, 8) void k_asym_score(AsymParams p) {
   __shared__ unsigned asym_cnt[kAsymMaxSub];
   constexpr int NT = kAsymThreads, R = kAsymR;
   const int tid = threadIdx.x;
-  const int tile = blockIdx.x / p.n_sub, s0 = (blockIdx.x % p.n_sub) * p.sub;
+  const SubRange g = sub_range(blockIdx.x, p.n_sub, p.sub, p.song_lo, p.song_hi, p.block_songs);
+  const int s0 = g.s0, sw = g.sw;
   const int u = p.user0 + blockIdx.y;
   const int width = p.song_hi - p.song_lo;
-  const int blo = p.song_lo + tile * p.block_songs;
-  const int bw = min(p.song_hi, blo + p.block_songs) - blo;
-  if (s0 >= bw) return;  // (block-uniform) the last tile is partial: no such sub-range
-  const int sw = min(p.sub, bw - s0);
-  const int* toff_t = p.toff + (size_t)tile * p.n_tr;
+  if (s0 >= g.bw) return;  // (block-uniform) the last tile is partial: no such sub-range
+  const int* toff_t = p.toff + (size_t)g.tile * p.n_tr;
   const long long t0 = p.te_off[u], t1 = p.te_off[u + 1];
 
-  const double* pow_a = p.pow_a + blo + s0;  // the sub-range's c(s)^alpha, read only where C >= 1
+  const double* pow_a = p.pow_a + g.blo + s0;  // the sub-range's c(s)^alpha, read only where C >= 1
   double acc[kAsymAcc];
 #pragma unroll
   for (int j = 0; j < kAsymAcc; ++j) acc[j] = 0.0;
   for (int i = tid; i < sw; i += NT) asym_cnt[i] = 0u;
   __syncthreads();
 
-  auto add = [&](int x) {
-    const unsigned loc = (unsigned)(x - s0);
+  auto add = [&](unsigned x, unsigned) {
+    const unsigned loc = x - (unsigned)s0;
     if (loc < (unsigned)sw)  // result unused: an LDS add without return
       (void)__hip_atomic_fetch_add(&asym_cnt[loc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
@@ -107,52 +96,15 @@ __global__ __launch_bounds__(kAsymThreads, 8) void k_asym_score(AsymParams p) {
     const int* lst = p.trs_users + l0;
     const double pb = p.pow_b[s2];
 
-    auto load_list = [&](int k0, int (&v)[R]) {
+    auto load_list = [&](int k0, int (&v)[R], unsigned (&w)[R]) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int k = k0 + r * NT;
         v[r] = k < n ? lst[k] : -1;
+        w[r] = 1u;
       }
     };
-    auto load_offs = [&](const int (&v)[R], int (&a)[R], int (&b)[R]) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        a[r] = b[r] = 0;
-        if (v[r] >= 0) { a[r] = toff_t[v[r]]; b[r] = toff_t[v[r] + 1]; }
-      }
-    };
-    int v0[R], a0[R], b0[R], v1[R], a1[R], b1[R], v2[R];
-    load_list(tid, v0);
-    load_offs(v0, a0, b0);
-    load_list(tid + R * NT, v1);
-    for (int k0 = tid; k0 < n; k0 += R * NT) {
-      int sg[R][kAsymSeg];
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int j = 0; j < kAsymSeg; ++j) sg[r][j] = a0[r] + j < b0[r] ? (int)p.tsongs[a0[r] + j] : -1;
-      load_offs(v1, a1, b1);             // iteration i+1
-      load_list(k0 + 2 * R * NT, v2);    // iteration i+2
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int j = 0; j < kAsymSeg; ++j)
-          if (sg[r][j] >= 0) add(sg[r][j]);
-        for (int x0 = a0[r] + kAsymSeg; x0 < b0[r]; x0 += kAsymSeg) {
-          int st[kAsymSeg];
-#pragma unroll
-          for (int j = 0; j < kAsymSeg; ++j) st[j] = x0 + j < b0[r] ? (int)p.tsongs[x0 + j] : -1;
-#pragma unroll
-          for (int j = 0; j < kAsymSeg; ++j)
-            if (st[j] >= 0) add(st[j]);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        a0[r] = a1[r]; b0[r] = b1[r];
-        v1[r] = v2[r];
-      }
-    }
+    walk_tile_lists<NT, R, kAsymSeg, unsigned, false>(tid, n, load_list, toff_t, p.tsongs, add);
     __syncthreads();
     // t = w^q by q - 1 multiplications, w = C / (c(s)^alpha * c(s2)^(1-alpha)); acc = acc + t
 #pragma unroll
@@ -162,11 +114,7 @@ __global__ __launch_bounds__(kAsymThreads, 8) void k_asym_score(AsymParams p) {
         const unsigned c = asym_cnt[i];
         if (c != 0u) {
           asym_cnt[i] = 0u;  // this thread alone reads and clears counter i
-          const double den = pow_a[i] * pb;
-          const double w = den != 0.0 ? (double)c / den : 0.0;
-          double t = w;
-          for (int k = 1; k < p.q; ++k) t = t * w;
-          acc[j] = acc[j] + t;
+          acc[j] = acc[j] + asym_weight(c, pow_a[i] * pb, p.q);
         }
       }
     }
@@ -175,35 +123,17 @@ __global__ __launch_bounds__(kAsymThreads, 8) void k_asym_score(AsymParams p) {
 
   // the heard songs of this sub-range (the counters are all zero here)
   for (long long i = t0 + tid; i < t1; i += NT) {
-    const unsigned loc = (unsigned)(p.te_songs[i] - (blo + s0));
+    const unsigned loc = (unsigned)(p.te_songs[i] - (g.blo + s0));
     if (loc < (unsigned)sw) asym_cnt[loc] = 1u;
   }
   __syncthreads();
-  const size_t o = (size_t)u * (size_t)width + (size_t)(blo + s0 - p.song_lo);
+  const size_t o = (size_t)u * (size_t)width + (size_t)(g.blo + s0 - p.song_lo);
 #pragma unroll
   for (int j = 0; j < kAsymAcc; ++j) {
     const int i = tid + j * NT;
-    if (i < sw) {
-      const bool heard = asym_cnt[i] != 0u;
-      if (p.f64)
-        static_cast<double*>(p.out)[o + i] = heard ? __longlong_as_double(0x7FF8000000000000ll) : acc[j];
-      else
-        static_cast<float*>(p.out)[o + i] = heard ? __int_as_float(0x7FC00000) : (float)acc[j];
-    }
+    if (i < sw) store_model_value(p.out, p.f64, o + i, asym_cnt[i] != 0u, acc[j]);
   }
 }
-
-template <typename T>
-struct Tmp {  // scratch device buffer of one call, stream-ordered
-  T* p = nullptr;
-  hipStream_t st = nullptr;
-  ~Tmp() { if (p) (void)hipFreeAsync(p, st); }
-};
-
-struct Drain {  // the call's host tables outlive their copies on every return path
-  hipStream_t st = nullptr;
-  ~Drain() { (void)hipStreamSynchronize(st); }
-};
 
 }  // namespace
 
@@ -233,41 +163,35 @@ int mr_asym_tables(double alpha, int32_t n, const int32_t* counts, double* pow_a
 
 int mr_ibm_asym_device(mr_ctx* ctx, double alpha, int32_t q, void* dense_dev) {
   if (!ctx) return fail(MR_E_INVALID, "null context");
-  if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(MR_E_INVALID, "alpha=%g must be in [0,1]", alpha);
-  if (q < 1 || q > MR_ASYM_MAX_Q) return fail(MR_E_INVALID, "q=%d must be in [1,%d]", q, MR_ASYM_MAX_Q);
-  if (!dense_dev) return fail(MR_E_INVALID, "null dense_dev");
-  mr_internal::AsymTables t;
-  int rc = mr_internal::asym_tables(ctx, &t);
+  int rc = mr_hip::check_asym_args(alpha, q);
   if (rc) return rc;
-  const mr_internal::SimilarTables& s = t.sim;
-  const int width = s.song_hi - s.song_lo;
+  if (!dense_dev) return fail(MR_E_INVALID, "null dense_dev");
+  mr_internal::ShardTables t;
+  if ((rc = mr_internal::shard_tables(ctx, "asymmetric item-based model", &t))) return rc;
+  const int width = t.song_hi - t.song_lo;
   if (t.n_te <= 0 || width <= 0) return MR_OK;
 
-  std::vector<double> pow_a((size_t)s.n_s), pow_b((size_t)s.n_s);
-  if ((rc = mr_asym_tables(alpha, s.n_s, t.song_count, pow_a.data(), pow_b.data()))) return rc;
+  std::vector<double> pow_a((size_t)t.n_s), pow_b((size_t)t.n_s);
+  if ((rc = mr_asym_tables(alpha, t.n_s, t.song_count, pow_a.data(), pow_b.data()))) return rc;
 
-  MR_HIP(hipSetDevice(s.device));
-  hipStream_t st = (hipStream_t)s.stream;
+  MR_HIP(hipSetDevice(t.device));
+  hipStream_t st = (hipStream_t)t.stream;
   Drain drain;
   drain.st = st;
   Tmp<double> d_a, d_b;
-  d_a.st = d_b.st = st;
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_a.p), (size_t)s.n_s * 8, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_b.p), (size_t)s.n_s * 8, st));
-  MR_HIP(hipMemcpyAsync(d_a.p, pow_a.data(), (size_t)s.n_s * 8, hipMemcpyHostToDevice, st));
-  MR_HIP(hipMemcpyAsync(d_b.p, pow_b.data(), (size_t)s.n_s * 8, hipMemcpyHostToDevice, st));
+  if ((rc = d_a.alloc((size_t)t.n_s, st)) || (rc = d_b.alloc((size_t)t.n_s, st))) return rc;
+  MR_HIP(hipMemcpyAsync(d_a.p, pow_a.data(), (size_t)t.n_s * 8, hipMemcpyHostToDevice, st));
+  MR_HIP(hipMemcpyAsync(d_b.p, pow_b.data(), (size_t)t.n_s * 8, hipMemcpyHostToDevice, st));
 
   // MR_ASYM_SUB (diagnostic): a smaller sub-range, so that small tiles take the multi-sub-range path
-  int cap = kAsymMaxSub;
-  if (const char* e = std::getenv("MR_ASYM_SUB")) cap = std::min(kAsymMaxSub, std::max(64, std::atoi(e)));
-  const int sub = std::min(s.block_songs, cap);
-  const int n_sub = (s.block_songs + sub - 1) / sub;
+  const int sub = std::min(t.block_songs, mr_hip::env_clamped("MR_ASYM_SUB", 64, kAsymMaxSub));
+  const int n_sub = (t.block_songs + sub - 1) / sub;
   const int rows = mr_internal::launch_rows(kAsymMaxBatch);  // (MR_LAUNCH_ROWS, diagnostic: fewer users per launch)
   for (int u0 = 0; u0 < t.n_te; u0 += rows) {
     const int nb = std::min(rows, t.n_te - u0);
-    AsymParams ap{s.n_tr,  s.song_lo,   s.song_hi, s.block_songs, sub,        n_sub,      q,     t.f64, u0,
-                  s.trs_off, s.trs_users, s.toff,    s.tsongs,      t.te_off,   t.te_songs, d_a.p, d_b.p, dense_dev};
-    hipLaunchKernelGGL(k_asym_score, dim3(s.n_tiles * n_sub, nb), dim3(kAsymThreads), 0, st, ap);
+    AsymParams ap{t.n_tr,    t.song_lo,   t.song_hi, t.block_songs, sub,      n_sub,      q,     t.f64, u0,
+                  t.trs_off, t.trs_users, t.toff,    t.tsongs,      t.te_off, t.te_songs, d_a.p, d_b.p, dense_dev};
+    hipLaunchKernelGGL(k_asym_score, dim3(t.n_tiles * n_sub, nb), dim3(kAsymThreads), 0, st, ap);
     MR_HIP(hipGetLastError());
   }
   MR_HIP(hipStreamSynchronize(st));

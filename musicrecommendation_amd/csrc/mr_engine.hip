@@ -50,11 +50,16 @@
 #endif
 
 #include "mr_engine.h"
+#include "mr_hip_util.h"
 #include "mr_internal.h"
 #include "mr_par.h"
+#include "mr_tile_walk.h"
 
 
 namespace {
+
+using mr_internal::kGridRows;
+using mr_internal::kGridRowsXcd;
 
 constexpr int kThreads = 256;             // 4 waves of 64
 constexpr int kWaves = kThreads / 64;
@@ -102,14 +107,6 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace mr_host
 
 namespace {
-
-#define MR_HIP(call)                                                                   \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return fail(e_ == hipErrorOutOfMemory ? MR_E_OOM : MR_E_HIP, "%s failed: %s (%s:%d)", \
-                  #call, hipGetErrorString(e_), __FILE__, __LINE__);                   \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // LDS layout of k_score (bytes; every region 16-byte aligned).
@@ -1846,93 +1843,14 @@ constexpr int kCoocBigRow = MR_COOC_BIG_ROW;  // listeners from which a heavy ro
 constexpr unsigned kCoocCntMask = (1u << kCoocCntBits) - 1u;
 constexpr int kCoocMaxTile = 1 << (32 - kCoocCntBits);
 
-
-// Stage 2 of the wide shape as a walk over a list of train users: entry k <
-// cnt of the list is (v, w) = load_list(k) (v = -1 past the end); every
-// tile-local song x of v's segment in this tile (tsongs[toff_t[v] ..
-// toff_t[v+1])) gets acc[x] += w by an LDS atomic. R entries per thread per
-// iteration. Used by the two-hop scoring (list = the test user's neighbours,
-// w = their int64 weights) and by the co-listening index build (list = one
-// song's train listeners, w = 1).
-template <int NT, int R, int kSeg, typename WT, typename LoadList, typename Add>
-__device__ __forceinline__ void walk_tile_lists(int tid, int cnt, LoadList&& load_list, const int* toff_t,
-                                                const unsigned short* tsongs, Add&& add) {
-  // Software pipeline over iterations: iteration i gathers its segments
-  // while the toff pairs of i+1 and the list entries of i+2 are in flight
-  // (one memory latency covers the three dependent levels).
-  auto load_offs = [&](const int (&v)[R], int (&a)[R], int (&b)[R]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      a[r] = b[r] = 0;
-      if (v[r] >= 0) { a[r] = toff_t[v[r]]; b[r] = toff_t[v[r] + 1]; }
-    }
-  };
-  int v0[R], a0[R], b0[R], v1[R], a1[R], b1[R], v2[R];
-  WT q0[R], q1[R], q2[R];
-  load_list(tid, v0, q0);
-  load_offs(v0, a0, b0);
-  load_list(tid + R * NT, v1, q1);
-  for (int k0 = tid; k0 < cnt; k0 += R * NT) {
+// walk_tile_lists (mr_tile_walk.h) in the two-hop scoring and the co-listening
+// index build: the 8-B word form of the segment loads, unless MR_WIDE_U16
+// builds the 2-B form (A/B).
 #ifndef MR_WIDE_U16
-    // a segment's first kSeg entries as 8-B words (4 tile-local ids each)
-    // from the aligned word holding entry a0: kW loads instead of kSeg
-    // 2-B loads (C4 21.9 vs 22.9 ms per 704-user batch, C3 1.093 vs 1.141 ms
-    // per step; MR_WIDE_U16 builds the 2-B form, profiles/r02/c4/vec_seg_ab.txt)
-    constexpr int kW = (kSeg + 3) / 4 + 1;
-    const uint2* tw = reinterpret_cast<const uint2*>(tsongs);
-    uint2 sw[R][kW];
-    int so[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int wb = a0[r] >> 2;
-      const int we = b0[r] > a0[r] ? (b0[r] + 3) >> 2 : wb;
-      so[r] = a0[r] & 3;
-#pragma unroll
-      for (int j = 0; j < kW; ++j) sw[r][j] = wb + j < we ? tw[wb + j] : make_uint2(0u, 0u);
-    }
+constexpr bool kWideWordSeg = true;
 #else
-    int sg[R][kSeg];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int j = 0; j < kSeg; ++j) sg[r][j] = a0[r] + j < b0[r] ? (int)tsongs[a0[r] + j] : -1;
+constexpr bool kWideWordSeg = false;
 #endif
-    load_offs(v1, a1, b1);                 // iteration i+1
-    load_list(k0 + 2 * R * NT, v2, q2);    // iteration i+2
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#ifndef MR_WIDE_U16
-#pragma unroll
-      for (int j = 0; j < kSeg; ++j) {
-        if (a0[r] + j < b0[r]) {
-          const int e = (j & 3) + so[r];  // 0..6: word j/4 or the next one
-          const uint2 wv = e >= 4 ? sw[r][(j >> 2) + 1] : sw[r][j >> 2];
-          const unsigned x = ((e & 3) < 2 ? wv.x : wv.y) >> ((e & 1) * 16);
-          add(x & 0xffffu, q0[r]);
-        }
-      }
-#else
-#pragma unroll
-      for (int j = 0; j < kSeg; ++j)
-        if (sg[r][j] >= 0) add((unsigned)sg[r][j], q0[r]);
-#endif
-      for (int x0 = a0[r] + kSeg; x0 < b0[r]; x0 += kSeg) {
-        int st[kSeg];
-#pragma unroll
-        for (int j = 0; j < kSeg; ++j) st[j] = x0 + j < b0[r] ? (int)tsongs[x0 + j] : -1;
-#pragma unroll
-        for (int j = 0; j < kSeg; ++j)
-          if (st[j] >= 0) add((unsigned)st[j], q0[r]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      a0[r] = a1[r]; b0[r] = b1[r]; q0[r] = q1[r];
-      v1[r] = v2[r]; q1[r] = q2[r];
-    }
-  }
-  (void)v0;
-}
 
 // Candidate-only tile top-k of the wide kernel, for top-k-only runs (no
 // dense row, no min / max): the epilogue computes the exact fp64 score of
@@ -2429,8 +2347,9 @@ __global__ __launch_bounds__(NT) void k_score_wide(ScoreParams p) {
         }
       }
     };
-    walk_tile_lists<NT, R, kSeg, unsigned long long>(tid, cnt, load_list, p.toff + (size_t)tile * p.n_tr, p.tsongs,
-                                                     [&](unsigned x, unsigned long long q) { atomicAdd(&acc[x], q); });
+    walk_tile_lists<NT, R, kSeg, unsigned long long, kWideWordSeg>(
+        tid, cnt, load_list, p.toff + (size_t)tile * p.n_tr, p.tsongs,
+        [&](unsigned x, unsigned long long q) { atomicAdd(&acc[x], q); });
   }
   __syncthreads();
   MR_STAMP(2);
@@ -2846,20 +2765,20 @@ __global__ __launch_bounds__(NT, (P16 ? 4 : 2) * NT / 256) void k_cooc_build(Coo
     for (int i = tid; i < cooc_words<P16>(bw); i += NT) cnt[i] = 0u;
     if (tid == 0) { *s_nz = 0; *s_tail = 0; }
     __syncthreads();
-    walk_tile_lists<NT, R, kSeg, unsigned>(tid, n, load_list, p.toff + (size_t)tile * p.n_tr, p.tsongs,
-                                           [&](unsigned x, unsigned) {
-                                             bool first;
-                                             if constexpr (P16) {
-                                               const unsigned sh = (x & 1) << 4;
-                                               first = ((atomicAdd(&cnt[x >> 1], 1u << sh) >> sh) & 0xffffu) == 0u;
-                                             } else {
-                                               first = atomicAdd(&cnt[x], 1u) == 0u;
-                                             }
-                                             if (first) {
-                                               const int k = atomicAdd(s_nz, 1);
-                                               if (k < kCap) touched[k] = (unsigned short)x;
-                                             }
-                                           });
+    walk_tile_lists<NT, R, kSeg, unsigned, kWideWordSeg>(
+        tid, n, load_list, p.toff + (size_t)tile * p.n_tr, p.tsongs, [&](unsigned x, unsigned) {
+          bool first;
+          if constexpr (P16) {
+            const unsigned sh = (x & 1) << 4;
+            first = ((atomicAdd(&cnt[x >> 1], 1u << sh) >> sh) & 0xffffu) == 0u;
+          } else {
+            first = atomicAdd(&cnt[x], 1u) == 0u;
+          }
+          if (first) {
+            const int k = atomicAdd(s_nz, 1);
+            if (k < kCap) touched[k] = (unsigned short)x;
+          }
+        });
     __syncthreads();
     if (tile == t_begin) stamp_rt(sb, 1);  // the first tile's walk done
     const int total = *s_nz;
@@ -4534,7 +4453,7 @@ int plan_launch(const mr_options& opt, int n_tr, int n_te, int n_s, size_t free_
   const size_t budget = std::min<size_t>((size_t)32 << 30, std::max<size_t>((size_t)8 << 30, free_b / 8)) /
                         (size_t)std::max(1, dev_share);
   p.batch = fused ? n_te
-                  : (int)std::max<size_t>(1, std::min<size_t>(std::min(n_te, 65528), budget / ((size_t)p.cap * 12)));
+                  : (int)std::max<size_t>(1, std::min<size_t>(std::min(n_te, kGridRowsXcd), budget / ((size_t)p.cap * 12)));
   if (const int cap_users = fused ? 0 : batch_users_opt()) p.batch = std::min(p.batch, cap_users);
   return MR_OK;
 }
@@ -5070,7 +4989,7 @@ int alloc_outputs(mr_ctx* c, const LaunchPlan& lp, int route, int n_te) {
   if (k > 0) {
     // wide: per-tile candidates of one launch (a neighbour batch; the
     // co-listening route launches up to 65528 users at once)
-    const int cand_users = !lp.wide() ? n_te : route == 2 ? std::max(lp.batch, std::min(n_te, 65528)) : lp.batch;
+    const int cand_users = !lp.wide() ? n_te : route == 2 ? std::max(lp.batch, std::min(n_te, kGridRowsXcd)) : lp.batch;
     const size_t nc = (size_t)cand_users * lp.n_tiles * k;
     if ((rc = dev_alloc(c->cand_key, nc))) return rc;
     if ((rc = dev_alloc(c->cand_song, nc))) return rc;
@@ -5305,7 +5224,7 @@ int mr_load(mr_ctx* c, const mr_dataset* d) {
   if ((rc = setup_kernels(c, lp, n_tr))) return rc;
 #ifdef MR_STAMPS
   // scoring workgroups' slots, then (co-listening route) 8 per k_cooc_build workgroup
-  const size_t stamp_users = (size_t)std::max(lp.batch, c->cooc.route == 2 ? std::min(n_te, 65528) : 0) + 8;
+  const size_t stamp_users = (size_t)std::max(lp.batch, c->cooc.route == 2 ? std::min(n_te, kGridRowsXcd) : 0) + 8;
   // scoring workgroups, then 8 per build workgroup (per (row, tile) bound + slack for the
   // group grid's padding), then 8 per light row
   const size_t build_wgs = (size_t)c->cooc.n_heavy() * lp.n_tiles + 64 * (size_t)std::max(1, lp.n_tiles);
@@ -5581,7 +5500,7 @@ int run_cooc(mr_ctx* c) {
       }
   }
   if (timed) MR_HIP(hipEventRecord(ev[1], st));
-  const int rows = mr_internal::launch_rows(65528);
+  const int rows = mr_internal::launch_rows(kGridRowsXcd);
   for (int y0 = 0; y0 < c->n_te; y0 += rows) {
     const int ny = std::min(rows, c->n_te - y0);
     const int remap = wide_map_opt();
@@ -5642,7 +5561,8 @@ int run_model(mr_ctx* c, int model) {
   const bool timed = c->opt.time_kernels != 0;
   const int k = c->opt.topk;
   // rows per launch: stage 1 (plain grid), scoring (grid padded to 8 users under the XCD remap)
-  const int rows1 = mr_internal::launch_rows(65535), rows = mr_internal::launch_rows(65528);
+  const int rows1 = mr_internal::launch_rows(kGridRows);
+  const int rows = mr_internal::launch_rows(kGridRowsXcd);
   for (int user0 = 0; user0 < c->n_te; user0 += c->batch) {
     const int nb = std::min(c->batch, c->n_te - user0);
     hipEvent_t* ev = nullptr;
@@ -5809,7 +5729,7 @@ int launch_merge(mr_ctx* c, int32_t n_shards, int32_t n_te, int32_t k, const Mer
   const int lds = merge_lds_bytes(k);
   if (lds > 160 * 1024) return fail(MR_E_INVALID, "merge of %d lists x %d needs too much LDS", n_shards, k);
   MR_HIP(hipFuncSetAttribute((const void*)k_topk_merge, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const int rows = launch_rows(65535);
+  const int rows = launch_rows(kGridRows);
   for (int y0 = 0; y0 < n_te; y0 += rows) {
     MergeParams q = mp;
     q.keys += (size_t)y0 * k;
@@ -5866,36 +5786,23 @@ int launch_rows(int production_max) {
   return n >= 8 ? std::min(production_max, n / 8 * 8) : production_max;
 }
 
-int similar_tables(mr_ctx* c, SimilarTables* out) {
+int shard_tables(mr_ctx* c, const char* what, ShardTables* out) {
   if (!c || !out) return fail(MR_E_INVALID, "null argument");
-  if (!c->loaded) return fail(MR_E_STATE, "similar-song query before mr_load");
-  *out = SimilarTables{c->n_tr,       c->n_s,         c->song_lo, c->song_hi,  c->block_songs, c->n_tiles, c->opt.device,
-                       c->trs_off.p,  c->trs_users.p, c->toff.p,  c->tsongs.p, c->sqrt_c.p,    c->stream};
-  return MR_OK;
-}
-
-int asym_tables(mr_ctx* c, AsymTables* out) {
-  if (!c || !out) return fail(MR_E_INVALID, "null argument");
-  if (!c->loaded) return fail(MR_E_STATE, "asymmetric item-based model before mr_load");
-  int rc = similar_tables(c, &out->sim);
-  if (rc) return rc;
-  out->n_te = c->n_te;
-  out->f64 = c->opt.out_dtype == MR_OUT_F64;
-  out->te_off = c->te_off.p;
-  out->te_songs = c->te_songs.p;
-  out->song_count = c->song_count.data();
-  return MR_OK;
-}
-
-int uasym_tables(mr_ctx* c, UasymTables* out) {
-  if (!c || !out) return fail(MR_E_INVALID, "null argument");
-  if (!c->loaded) return fail(MR_E_STATE, "asymmetric user-based model before mr_load");
-  int rc = asym_tables(c, &out->asym);
-  if (rc) return rc;
-  out->te_len = c->te_len_h.data();
-  out->tr_len = c->tr_len_h.data();
-  out->max_ctr = c->max_ctr;
-  out->frac_bits = c->opt.frac_bits;
+  if (!c->loaded) return fail(MR_E_STATE, "%s before mr_load", what);
+  ShardTables& t = *out;
+  t.n_tr = c->n_tr; t.n_te = c->n_te; t.n_s = c->n_s;
+  t.song_lo = c->song_lo; t.song_hi = c->song_hi; t.block_songs = c->block_songs; t.n_tiles = c->n_tiles;
+  t.device = c->opt.device;
+  t.f64 = c->opt.out_dtype == MR_OUT_F64;
+  t.frac_bits = c->opt.frac_bits;
+  t.max_ctr = c->max_ctr;
+  t.stream = c->stream;
+  t.trs_off = c->trs_off.p; t.trs_users = c->trs_users.p;
+  t.toff = c->toff.p; t.tsongs = c->tsongs.p;
+  t.sqrt_c = c->sqrt_c.p;
+  t.te_off = c->te_off.p; t.te_songs = c->te_songs.p;
+  t.song_count = c->song_count.data();
+  t.te_len = c->te_len_h.data(); t.tr_len = c->tr_len_h.data();
   return MR_OK;
 }
 
@@ -6191,7 +6098,7 @@ int mr_topk_dense_device(mr_ctx* c, const void* dense_dev, int32_t k) {
   MR_HIP(hipSetDevice(c->opt.device));
   MR_HIP(hipMemsetAsync(c->flag.p, 0, sizeof(unsigned), c->stream));
   const bool f64 = c->opt.out_dtype == MR_OUT_F64;
-  const int rows = mr_internal::launch_rows(65535);
+  const int rows = mr_internal::launch_rows(kGridRows);
   for (int y0 = 0; y0 < c->n_te; y0 += rows) {
     DenseTopkParams tp{y0, c->width, c->song_lo, k, dense_dev, c->top_key.p, c->top_song.p, c->top_score.p,
                        c->flag.p};

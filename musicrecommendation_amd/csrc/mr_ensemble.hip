@@ -22,23 +22,13 @@
 #include <vector>
 
 #include "mr_engine.h"
+#include "mr_hip_util.h"
 #include "mr_internal.h"
-
-namespace mr_host {
-int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
-}
 
 namespace {
 
+using mr_hip::Tmp;
 using mr_host::fail;
-
-#define MR_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(e_ == hipErrorOutOfMemory ? MR_E_OOM : MR_E_HIP, "%s failed: %s (%s:%d)", #call, \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-  } while (0)
 
 constexpr int kThreads = 256;
 // Thresholds: the first n of 0.0, 0.1, ..., 1.0 — n = 10 for MusicRecommender's
@@ -423,13 +413,6 @@ __global__ __launch_bounds__(kThreads) void k_eval_gather(int n_cls, int n_thr, 
   out[(size_t)n_cls * n_thr + j] = in ? tp[(size_t)g * n_thr + t] : 0;
 }
 
-template <typename T>
-struct Tmp {  // scratch device buffer of one call, stream-ordered (pool allocator: no device sync)
-  T* p = nullptr;
-  hipStream_t st = nullptr;
-  ~Tmp() { if (p) (void)hipFreeAsync(p, st); }
-};
-
 // The label CSR of the context's test users as (user, song) pairs, one per
 // label (at least one slot, so the staging buffers are never empty).
 int label_pairs(int n_te, const int64_t* lab_off, const int32_t* lab_songs, std::vector<int32_t>& lu,
@@ -470,12 +453,11 @@ int eval_counts(mr_ctx* ctx, int n_models, const void* const* dense, const doubl
   const long long n_lab = lab_off[n_te];
   hipStream_t st = (hipStream_t)v.stream;
   Tmp<int> d_lu, d_ls;
-  d_pred.st = d_tp.st = d_lu.st = d_ls.st = st;
   const size_t nc = (size_t)width * n_thr;
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_pred.p), std::max<size_t>(1, nc) * 4, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_tp.p), std::max<size_t>(1, nc) * 4, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_lu.p), lu.size() * 4, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ls.p), ls.size() * 4, st));
+  if (int rc_ = d_pred.alloc(std::max<size_t>(1, nc), st)) return rc_;
+  if (int rc_ = d_tp.alloc(std::max<size_t>(1, nc), st)) return rc_;
+  if (int rc_ = d_lu.alloc(lu.size(), st)) return rc_;
+  if (int rc_ = d_ls.alloc(ls.size(), st)) return rc_;
   MR_HIP(hipMemcpyAsync(d_lu.p, lu.data(), lu.size() * 4, hipMemcpyHostToDevice, st));
   MR_HIP(hipMemcpyAsync(d_ls.p, ls.data(), ls.size() * 4, hipMemcpyHostToDevice, st));
   // (song block x user block) workgroups: ~1024 of them fill the chip (a
@@ -885,8 +867,7 @@ struct Sweep {
     sp.te_songs = v.te_songs;
     sp.ubm = ubm;
     sp.ibm = ibm;
-    d_tab.st = st;
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_tab.p), sizeof(SweepTab), st));
+    if (int rc_ = d_tab.alloc(1, st)) return rc_;
     sp.tab = d_tab.p;
     return MR_OK;
   }
@@ -906,9 +887,8 @@ struct Sweep {
     const int gy = std::max(1, std::min(sp.n_te, (8192 + gx - 1) / gx));
     const long long nblk = (long long)gx * gy;
     Tmp<double> part, out;
-    part.st = out.st = st;
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part.p), (size_t)nblk * n_params * 2 * sizeof(double), st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&out.p), (size_t)n_params * 2 * sizeof(double), st));
+    if (int rc_ = part.alloc((size_t)nblk * n_params * 2, st)) return rc_;
+    if (int rc_ = out.alloc((size_t)n_params * 2, st)) return rc_;
     SweepParams q = sp;
     q.part = part.p;
     MR_SWEEP_LAUNCH(k_sweep_minmax, f64, kind, dim3(gx, gy), st, q);
@@ -949,16 +929,15 @@ struct Sweep {
       return MR_OK;
     }
     Tmp<int> d_pred, d_tp, d_lu, d_ls, d_cls;
-    d_pred.st = d_tp.st = d_lu.st = d_ls.st = d_cls.st = st;
     const size_t nc = (size_t)kSweepG * width * n_thr;
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_pred.p), nc * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_tp.p), nc * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_lu.p), lu.size() * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ls.p), ls.size() * 4, st));
+    if (int rc_ = d_pred.alloc(nc, st)) return rc_;
+    if (int rc_ = d_tp.alloc(nc, st)) return rc_;
+    if (int rc_ = d_lu.alloc(lu.size(), st)) return rc_;
+    if (int rc_ = d_ls.alloc(ls.size(), st)) return rc_;
     MR_HIP(hipMemcpyAsync(d_lu.p, lu.data(), lu.size() * 4, hipMemcpyHostToDevice, st));
     MR_HIP(hipMemcpyAsync(d_ls.p, ls.data(), ls.size() * 4, hipMemcpyHostToDevice, st));
     if (n_classes > 0) {
-      MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cls.p), (size_t)n_classes * 4, st));
+      if (int rc_ = d_cls.alloc((size_t)n_classes, st)) return rc_;
       MR_HIP(hipMemcpyAsync(d_cls.p, classes, (size_t)n_classes * 4, hipMemcpyHostToDevice, st));
     }
     // the workgroup shape of eval_counts: users split only when the songs alone give too few workgroups
@@ -1023,7 +1002,7 @@ int mr_combine_device(mr_ctx* ctx, int kind, double param, uint64_t seed, int64_
                 (long long)pair_base, (long long)(param * (double)n_pairs),  // (p * length).toInt, MR:371
                 reinterpret_cast<const long long*>(v.te_off), v.te_songs, ubm, ibm, out};
   hipStream_t st = (hipStream_t)v.stream;
-  const int rows = mr_internal::launch_rows(65535);
+  const int rows = mr_internal::launch_rows(mr_internal::kGridRows);
   for (int y0 = 0; y0 < v.n_test_users; y0 += rows) {
     CombParams q = cp;
     const int ny = std::min(rows, v.n_test_users - y0);
@@ -1067,13 +1046,12 @@ int mr_combine_all_device(mr_ctx* ctx, double alpha, double ibm_percentage, doub
   const int gx = (width + kThreads * kCombPer - 1) / (kThreads * kCombPer);
   const long long nblk = (long long)gx * v.n_test_users;
   Tmp<double> part, part2;
-  part.st = part2.st = st;
   constexpr int kRed = 256;  // k_minmax6 blocks
   if (minmax && nblk > 0) {
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part.p), (size_t)nblk * 6 * sizeof(double), st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part2.p), (size_t)kRed * 6 * sizeof(double), st));
+    if (int rc_ = part.alloc((size_t)nblk * 6, st)) return rc_;
+    if (int rc_ = part2.alloc((size_t)kRed * 6, st)) return rc_;
   }
-  const int rows = mr_internal::launch_rows(65535);
+  const int rows = mr_internal::launch_rows(mr_internal::kGridRows);
   for (int y0 = 0; gx > 0 && y0 < v.n_test_users; y0 += rows) {
     Comb3Params q = cp;
     const int ny = std::min(rows, v.n_test_users - y0);
@@ -1116,8 +1094,7 @@ int mr_eval_minmax_device(mr_ctx* ctx, const void* dense, double* mn, double* mx
   const int blocks = (int)std::max<long long>(1, std::min<long long>(4096, (n + kThreads - 1) / kThreads));
   hipStream_t st = (hipStream_t)v.stream;
   Tmp<double> part;
-  part.st = st;
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part.p), (size_t)blocks * 2 * sizeof(double), st));
+  if (int rc_ = part.alloc((size_t)blocks * 2, st)) return rc_;
   if (v.out_dtype == MR_OUT_F64)
     hipLaunchKernelGGL(k_minmax<double>, dim3(blocks), dim3(kThreads), 0, st, (const double*)dense, n, part.p);
   else
@@ -1171,12 +1148,11 @@ int mr_eval_map_device(mr_ctx* ctx, const void* dense, double mn, double mx, con
   const int nc = (int)cls.size();
   Tmp<int> d_cls, d_cpos;
   Tmp<double> d_ap;
-  d_cls.st = d_cpos.st = d_ap.st = st;
   std::vector<double> ap((size_t)std::max(1, nc));
   if (nc > 0) {
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cls.p), (size_t)nc * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cpos.p), (size_t)nc * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ap.p), (size_t)nc * 8, st));
+    if (int rc_ = d_cls.alloc((size_t)nc, st)) return rc_;
+    if (int rc_ = d_cpos.alloc((size_t)nc, st)) return rc_;
+    if (int rc_ = d_ap.alloc((size_t)nc, st)) return rc_;
     MR_HIP(hipMemcpyAsync(d_cls.p, cls.data(), (size_t)nc * 4, hipMemcpyHostToDevice, st));
     MR_HIP(hipMemcpyAsync(d_cpos.p, cpos.data(), (size_t)nc * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_eval_ap, dim3((nc + kThreads - 1) / kThreads), dim3(kThreads), 0, st, nc, n_thr, d_cls.p,
@@ -1205,8 +1181,7 @@ int mr_eval_class_counts_device(mr_ctx* ctx, int32_t n_models, const void* const
     if (n_classes == 0) return 0;
     hipStream_t st = (hipStream_t)v.stream;
     if (!d_cls.p) {  // the class list, staged once (after eval_counts resolved the context)
-      d_cls.st = st;
-      MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cls.p), (size_t)n_classes * 4, st));
+      if (int rc_ = d_cls.alloc((size_t)n_classes, st)) return rc_;
       MR_HIP(hipMemcpyAsync(d_cls.p, classes, (size_t)n_classes * 4, hipMemcpyHostToDevice, st));
     }
     const int n = n_classes * n_thr;
@@ -1250,10 +1225,9 @@ int mr_eval_map_counts_device(mr_ctx* ctx, int32_t n_models, int32_t n_classes, 
       }
     Tmp<int> d_cls, d_cpos;
     Tmp<double> d_ap;
-    d_cls.st = d_cpos.st = d_ap.st = st;
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cls.p), nap * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cpos.p), nap * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ap.p), nap * 8, st));
+    if (int rc_ = d_cls.alloc(nap, st)) return rc_;
+    if (int rc_ = d_cpos.alloc(nap, st)) return rc_;
+    if (int rc_ = d_ap.alloc(nap, st)) return rc_;
     MR_HIP(hipMemcpyAsync(d_cls.p, cls.data(), nap * 4, hipMemcpyHostToDevice, st));
     MR_HIP(hipMemcpyAsync(d_cpos.p, cpos.data(), nap * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_eval_ap, dim3((unsigned)((nap + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (int)nap,
@@ -1323,9 +1297,8 @@ int mr_sweep_map_device(mr_ctx* ctx, int kind, int32_t n_params, const double* p
     if (pos[g] > 0) { cls.push_back(g); cpos.push_back(pos[g]); }
   const int nc = (int)cls.size();
   Tmp<int> d_counts;
-  d_counts.st = s.st;
   const size_t n = std::max<size_t>(1, (size_t)n_params * 2 * nc * n_thr);
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_counts.p), n * 4, s.st));
+  if (int rc_ = d_counts.alloc(n, s.st)) return rc_;
   if ((rc = s.class_counts(mn, mx, lab_off, lab_songs, nc, cls.data(), d_counts.p, n_thr))) return rc;
   return mr_eval_map_counts_device(ctx, n_params, nc, cpos.data(), d_counts.p, n_label_songs, maps_out, n_thr);
 }

@@ -38,47 +38,33 @@ int d2h_staged(mr_ctx* c, void* dst, size_t dpitch, const void* src, size_t spit
 // group's contexts measure free memory at once, before any of them allocates.
 int set_device_share(mr_ctx* c, int n);
 
-// The loaded tables a similar-song query reads (csrc/mr_similar.hip): device
-// pointers and geometry of the context's shard, valid until mr_load /
-// mr_destroy. MR_E_STATE before mr_load.
-struct SimilarTables {
-  int n_tr, n_s, song_lo, song_hi, block_songs, n_tiles, device;
+// The loaded tables of the context's shard that the models outside
+// mr_engine.hip read (csrc/mr_similar.hip, mr_asym.hip, mr_uasym.hip): geometry,
+// device pointers and the HOST copies mr_load keeps of mr_dataset.song_count,
+// te_len and tr_len (4 * (n_s + n_te + n_tr) bytes). Everything is valid until
+// mr_load / mr_destroy.
+struct ShardTables {
+  int n_tr, n_te, n_s, song_lo, song_hi, block_songs, n_tiles, device;
+  int f64;                       // != 0: the dense model is double, else float (mr_options.out_dtype)
+  int frac_bits;                 // mr_options.frac_bits of the context
+  int32_t max_ctr;               // max over every song s of c_tr(s) = |L_tr(s)|
+  void* stream;                  // the context's hipStream_t
+  // device
   const long long* trs_off;      // song -> train listeners CSR [n_s + 1] (every song, not only the shard's)
   const int* trs_users;          //   listeners as the context's (renumbered) train users, ascending
   const int* toff;               // tile-major train CSR over the shard [n_tiles * n_tr + 1]
   const unsigned short* tsongs;  //   tile-local song ids, rows duplicate-free
   const double* sqrt_c;          // sqrt(c(s)) [n_s] (train + test lines, duplicates counted)
-  void* stream;                  // the context's hipStream_t
+  const long long* te_off;       // test user -> distinct visible songs T(u) [n_te + 1]
+  const int* te_songs;           //   ascending song ids
+  // host
+  const int32_t* song_count;     // c(s) [n_s]
+  const int32_t* te_len;         // |T(u)| with duplicates [n_te]
+  const int32_t* tr_len;         // |S(v)| with duplicates [n_tr], v the context's internal train id (the ids
+                                 //   trs_users and toff are indexed by), not the dataset's train order
 };
-int similar_tables(mr_ctx* c, SimilarTables* out);
-
-// The same tables plus what the asymmetric item-based model reads
-// (csrc/mr_asym.hip): the test users' CSR on the device, the context's output
-// element type and the HOST copy of mr_dataset.song_count that mr_load keeps
-// (4 * n_s bytes). Valid until mr_load / mr_destroy. MR_E_STATE before mr_load.
-struct AsymTables {
-  SimilarTables sim;
-  int n_te, f64;               // f64 != 0: the dense model is double, else float
-  const long long* te_off;     // device: test user -> distinct visible songs T(u) [n_te + 1]
-  const int* te_songs;         //   ascending song ids
-  const int32_t* song_count;   // host: c(s) [n_s]
-};
-int asym_tables(mr_ctx* c, AsymTables* out);
-
-// The same tables plus what the asymmetric user-based model reads
-// (csrc/mr_uasym.hip): the HOST copies mr_load keeps of mr_dataset.te_len, of
-// tr_len in the context's internal train order (the ids trs_users and toff are
-// indexed by) and of the largest train-listener count of any song
-// (4 * (n_tr + n_te) bytes), and the context's mr_options.frac_bits. Valid
-// until mr_load / mr_destroy. MR_E_STATE before mr_load.
-struct UasymTables {
-  AsymTables asym;
-  const int32_t* te_len;  // host: |T(u)| with duplicates [n_te]
-  const int32_t* tr_len;  // host: |S(v)| with duplicates [n_tr], v the context's train id
-  int32_t max_ctr;        // max over every song s of c_tr(s) = |L_tr(s)|
-  int frac_bits;          // mr_options.frac_bits of the context
-};
-int uasym_tables(mr_ctx* c, UasymTables* out);
+// MR_E_STATE "<what> before mr_load" when the context has no dataset.
+int shard_tables(mr_ctx* c, const char* what, ShardTables* out);
 
 // k_rank_dense over n_rows rows of `width` values (f64 != 0: double, else
 // float; NaN = no entry) into songs / scores [n_rows][K] (scores may be NULL),
@@ -87,9 +73,14 @@ int uasym_tables(mr_ctx* c, UasymTables* out);
 int rank_rows_async(void* stream, int f64, int32_t n_rows, int32_t width, int32_t song_lo, const void* dense,
                     int32_t K, int32_t* songs, double* scores);
 
+// The grid-row limit (grid y <= 65535), and the limit where the XCD remap
+// pads the grid to a multiple of 8 rows.
+constexpr int kGridRows = 65535;
+constexpr int kGridRowsXcd = 65528;
+
 // Rows (grid y: test users or queries) of one launch of every host loop that
-// splits a call at the grid-row limit: production_max (65535, or 65528 where
-// the XCD remap pads the grid to a multiple of 8 rows), unless
+// splits a call at the grid-row limit: production_max (kGridRows, or
+// kGridRowsXcd under the XCD remap), unless
 // MR_LAUNCH_ROWS=n (diagnostic, n >= 8, read at each call) lowers it to n
 // rounded down to a multiple of 8, so that a few dozen rows take the second
 // and later iterations. Never below 8; any other value is ignored.

@@ -31,23 +31,13 @@
 #include <vector>
 
 #include "mr_engine.h"
+#include "mr_hip_util.h"
 #include "mr_internal.h"
-
-namespace mr_host {
-int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
-}
 
 namespace {
 
+using mr_hip::Tmp;
 using mr_host::fail;
-
-#define MR_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(e_ == hipErrorOutOfMemory ? MR_E_OOM : MR_E_HIP, "%s failed: %s (%s:%d)", #call, \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-  } while (0)
 
 constexpr int kRankThreads = 1024;
 constexpr int kRankWaves = kRankThreads / 64;
@@ -323,13 +313,6 @@ __global__ __launch_bounds__(kMapThreads) void k_rank_map(int n_te, int K, int k
   if (lane == 0) ap[u] = n_u > 0 ? a / (double)(n_u < k_eval ? n_u : (long long)k_eval) : 0.0;
 }
 
-template <typename T>
-struct Tmp {  // scratch device buffer of one call, stream-ordered
-  T* p = nullptr;
-  hipStream_t st = nullptr;
-  ~Tmp() { if (p) (void)hipFreeAsync(p, st); }
-};
-
 // Sorted, distinct labels per user as a CSR (labels are a set).
 int distinct_labels(int n_te, const int64_t* lab_off, const int32_t* lab_songs, std::vector<long long>& off,
                     std::vector<int32_t>& songs) {
@@ -477,11 +460,10 @@ int mr_rank_map_device(mr_ctx* ctx, const int32_t* songs_dev, int32_t K, int32_t
   Tmp<long long> d_off;
   Tmp<int> d_lab;
   Tmp<double> d_ap;
-  d_off.st = d_lab.st = d_ap.st = st;
   if (n_te > 0) {
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_off.p), off.size() * 8, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_lab.p), lab.size() * 4, st));
-    MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ap.p), (size_t)n_te * 8, st));
+    if (int rc_ = d_off.alloc(off.size(), st)) return rc_;
+    if (int rc_ = d_lab.alloc(lab.size(), st)) return rc_;
+    if (int rc_ = d_ap.alloc((size_t)n_te, st)) return rc_;
     MR_HIP(hipMemcpyAsync(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
     MR_HIP(hipMemcpyAsync(d_lab.p, lab.data(), lab.size() * 4, hipMemcpyHostToDevice, st));
     const int per = kMapThreads / 64;

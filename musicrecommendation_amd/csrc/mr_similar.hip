@@ -10,11 +10,10 @@
 //   2. the workgroup walks the query's train listeners L_tr(q) =
 //      trs_users[trs_off[q] .. trs_off[q+1]): listener v's songs in this tile
 //      are tsongs[toff[t*n_tr+v] .. toff[t*n_tr+v+1]), and every one of them
-//      gets +1 by an LDS add without a returned value. Three dependent levels
-//      (listener id -> toff pair -> segment ids) are software-pipelined: while
-//      iteration i's segments are consumed, the toff pairs of i+1 and the
-//      listener ids of i+2 are in flight (the pattern of the engine's
-//      walk_tile_lists). Rows of the tile CSR are duplicate-free, so a listener
+//      gets +1 by an LDS add without a returned value. The walk is the shared
+//      walk_tile_lists (csrc/mr_tile_walk.h: listener id -> toff pair ->
+//      segment ids, software-pipelined three levels deep) in its 2-byte
+//      segment-load form. Rows of the tile CSR are duplicate-free, so a listener
 //      adds at most 1 per song: the counter is C(q, s) = |L_tr(q) ∩ L_tr(s)|;
 //   3. the epilogue writes (double)C / (sqrt_c[q] * sqrt_c[s]) (0.0 for a zero
 //      denominator; fp64 * and / only, no contraction) coalesced to the dense
@@ -26,32 +25,22 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
 #include "mr_engine.h"
+#include "mr_hip_util.h"
 #include "mr_internal.h"
-
-namespace mr_host {
-int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
-}
+#include "mr_tile_walk.h"
 
 namespace {
 
+using mr_hip::Tmp;
 using mr_host::fail;
-
-#define MR_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(e_ == hipErrorOutOfMemory ? MR_E_OOM : MR_E_HIP, "%s failed: %s (%s:%d)", #call, \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-  } while (0)
 
 constexpr int kSimThreads = 1024;
 constexpr int kSimR = 2;                  // listeners per thread and iteration
 constexpr int kSimSeg = 4;                // segment ids loaded together
 constexpr int kSimMaxCounters = 32768;    // u32 counters per pass: 128 KiB of the CU's 160 KiB LDS
-constexpr int kSimMaxBatch = 65535;       // queries per launch (grid y)
+constexpr int kSimMaxBatch = mr_internal::kGridRows;  // queries per launch (grid y)
 static_assert(MR_SIMILAR_SCRATCH_BYTES >= 8, "one value");
 
 struct SimParams {
@@ -81,18 +70,12 @@ __global__ __launch_bounds__(kSimThreads) void k_similar_count(SimParams p) {
   const double sq = p.sqrt_c[q];
   const double nan = __longlong_as_double(0x7FF8000000000000ll);
 
-  auto load_list = [&](int k0, int (&v)[R]) {
+  auto load_list = [&](int k0, int (&v)[R], unsigned (&w)[R]) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int k = k0 + r * NT;
       v[r] = k < n ? lst[k] : -1;
-    }
-  };
-  auto load_offs = [&](const int (&v)[R], int (&a)[R], int (&b)[R]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      a[r] = b[r] = 0;
-      if (v[r] >= 0) { a[r] = toff_t[v[r]]; b[r] = toff_t[v[r] + 1]; }
+      w[r] = 1u;
     }
   };
 
@@ -100,44 +83,12 @@ __global__ __launch_bounds__(kSimThreads) void k_similar_count(SimParams p) {
     const int sw = min(p.sub, bw - s0);
     for (int i = tid; i < sw; i += NT) sim_cnt[i] = 0u;
     __syncthreads();
-    auto add = [&](int x) {
-      const unsigned loc = (unsigned)(x - s0);
+    auto add = [&](unsigned x, unsigned) {
+      const unsigned loc = x - (unsigned)s0;
       if (loc < (unsigned)sw)  // result unused: an LDS add without return
         (void)__hip_atomic_fetch_add(&sim_cnt[loc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    int v0[R], a0[R], b0[R], v1[R], a1[R], b1[R], v2[R];
-    load_list(tid, v0);
-    load_offs(v0, a0, b0);
-    load_list(tid + R * NT, v1);
-    (void)v0;
-    for (int k0 = tid; k0 < n; k0 += R * NT) {
-      int sg[R][kSimSeg];
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int j = 0; j < kSimSeg; ++j) sg[r][j] = a0[r] + j < b0[r] ? (int)p.tsongs[a0[r] + j] : -1;
-      load_offs(v1, a1, b1);             // iteration i+1
-      load_list(k0 + 2 * R * NT, v2);    // iteration i+2
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int j = 0; j < kSimSeg; ++j)
-          if (sg[r][j] >= 0) add(sg[r][j]);
-        for (int x0 = a0[r] + kSimSeg; x0 < b0[r]; x0 += kSimSeg) {
-          int st[kSimSeg];
-#pragma unroll
-          for (int j = 0; j < kSimSeg; ++j) st[j] = x0 + j < b0[r] ? (int)p.tsongs[x0 + j] : -1;
-#pragma unroll
-          for (int j = 0; j < kSimSeg; ++j)
-            if (st[j] >= 0) add(st[j]);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        a0[r] = a1[r]; b0[r] = b1[r];
-        v1[r] = v2[r];
-      }
-    }
+    walk_tile_lists<NT, R, kSimSeg, unsigned, false>(tid, n, load_list, toff_t, p.tsongs, add);
     __syncthreads();
     // cos(q, s) = C / (sqrt(c(q)) * sqrt(c(s))), MR:236-238
     for (int i = tid; i < sw; i += NT) {
@@ -153,13 +104,6 @@ __global__ __launch_bounds__(kSimThreads) void k_similar_count(SimParams p) {
   }
 }
 
-template <typename T>
-struct Tmp {  // scratch device buffer of one call, stream-ordered
-  T* p = nullptr;
-  hipStream_t st = nullptr;
-  ~Tmp() { if (p) (void)hipFreeAsync(p, st); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -172,8 +116,8 @@ int mr_similar_songs_device(mr_ctx* ctx, int32_t n_q, const int32_t* query_songs
   if (n_q > 0 && !query_songs) return fail(MR_E_INVALID, "null query_songs");
   if (K == 0 && !dense_dev) return fail(MR_E_INVALID, "K = 0 needs dense_dev");
   if (K >= 1 && !songs_dev) return fail(MR_E_INVALID, "K >= 1 needs songs_dev");
-  mr_internal::SimilarTables t;
-  int rc = mr_internal::similar_tables(ctx, &t);
+  mr_internal::ShardTables t;
+  int rc = mr_internal::shard_tables(ctx, "similar-song query", &t);
   if (rc) return rc;
   for (int i = 0; i < n_q; ++i)
     if (query_songs[i] < 0 || query_songs[i] >= t.n_s)
@@ -190,15 +134,12 @@ int mr_similar_songs_device(mr_ctx* ctx, int32_t n_q, const int32_t* query_songs
                            (int64_t)MR_SIMILAR_SCRATCH_BYTES / (8 * (int64_t)width)));
   Tmp<int> d_q;
   Tmp<double> d_listed;
-  d_q.st = d_listed.st = st;
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_q.p), (size_t)n_q * 4, st));
+  if ((rc = d_q.alloc((size_t)n_q, st))) return rc;
   MR_HIP(hipMemcpyAsync(d_q.p, query_songs, (size_t)n_q * 4, hipMemcpyHostToDevice, st));
-  if (K >= 1) MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_listed.p), (size_t)per * width * 8, st));
+  if (K >= 1 && (rc = d_listed.alloc((size_t)per * width, st))) return rc;
 
   // MR_SIMILAR_COUNTERS (diagnostic): fewer counters per pass, so that small tiles take the sub-range path
-  int cap = kSimMaxCounters;
-  if (const char* e = std::getenv("MR_SIMILAR_COUNTERS")) cap = std::min(kSimMaxCounters, std::max(64, std::atoi(e)));
-  const int sub = std::min(t.block_songs, cap);
+  const int sub = std::min(t.block_songs, mr_hip::env_clamped("MR_SIMILAR_COUNTERS", 64, kSimMaxCounters));
   const size_t lds = (size_t)sub * 4;
   MR_HIP(hipFuncSetAttribute((const void*)k_similar_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (int b0 = 0; b0 < n_q; b0 += per) {

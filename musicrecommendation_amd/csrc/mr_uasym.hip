@@ -26,7 +26,8 @@
 //      workgroup that walks the tile's rows and keeps the ids of its range);
 //   2. thread tid takes the neighbours tid, tid + 1024, ... of every chunk's
 //      list and walks the neighbour's row of the tile-major train CSR (toff /
-//      tsongs), adding the key with a 64-bit LDS add without a returned value;
+//      tsongs) with the shared walk_tile_row (csrc/mr_tile_walk.h), adding the
+//      key with a 64-bit LDS add without a returned value;
 //   3. the heard songs of the range are marked and the row is stored
 //      coalesced: (double)acc * 2^-F, NaN where heard (f32: rounded once).
 // The overlaps and the scores are integer sums (order-free); every fp64
@@ -38,27 +39,19 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <vector>
 
 #include "mr_engine.h"
+#include "mr_hip_util.h"
 #include "mr_internal.h"
-
-namespace mr_host {
-int fail(int code, const char* fmt, ...);  // thread-local error slot (mr_engine.hip)
-}
+#include "mr_tile_walk.h"
 
 namespace {
 
+using mr_hip::Drain;
+using mr_hip::env_clamped;
+using mr_hip::Tmp;
 using mr_host::fail;
-
-#define MR_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(e_ == hipErrorOutOfMemory ? MR_E_OOM : MR_E_HIP, "%s failed: %s (%s:%d)", #call, \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-  } while (0)
 
 constexpr int kUwThreads = 512;                 // k_uasym_weights
 constexpr int kUwWaves = kUwThreads / 64;
@@ -66,7 +59,7 @@ constexpr int kUasymChunk = 8192;               // train users per chunk: 32 KiB
 constexpr int kUsThreads = 1024;                // k_uasym_score
 constexpr int kUsSeg = 4;                       // segment ids loaded together
 constexpr int kUasymMaxSub = 8192;              // songs per sub-range: 64 KiB of int64 accumulators
-constexpr int kUasymMaxBatch = 65535;           // test users per launch (grid y)
+constexpr int kUasymMaxBatch = mr_internal::kGridRows;  // test users per launch (grid y)
 constexpr unsigned long long kHeard = 0x8000000000000000ull;  // no sum reaches it (headroom rule)
 
 struct UwParams {
@@ -148,12 +141,8 @@ __global__ __launch_bounds__(kUwThreads) void k_uasym_weights(UwParams p) {
     if (y != 0u) {
       const int pos = base + __popcll(m & below);
       const int v = cv0 + i;
-      const double den = pa_u * p.pb[v];
-      const double wt = den != 0.0 ? (double)y / den : 0.0;
-      double t = wt;
-      for (int k = 1; k < p.q; ++k) t = t * wt;
       out_v[pos] = v;
-      out_k[pos] = (long long)rint(t * p.two_f);
+      out_k[pos] = (long long)rint(asym_weight(y, pa_u * p.pb[v], p.q) * p.two_f);
     }
     base += __popcll(m);
   }
@@ -179,22 +168,14 @@ __global__ __launch_bounds__(kUsThreads) void k_uasym_score(UsParams p) {
   __shared__ unsigned long long us_acc[kUasymMaxSub];
   constexpr int NT = kUsThreads;
   const int tid = threadIdx.x;
-  const int tile = blockIdx.x / p.n_sub, s0 = (blockIdx.x % p.n_sub) * p.sub;
+  const SubRange g = sub_range(blockIdx.x, p.n_sub, p.sub, p.song_lo, p.song_hi, p.block_songs);
+  const int s0 = g.s0, sw = g.sw;
   const int bu = p.r0 + blockIdx.y, u = p.u0 + bu;
   const int width = p.song_hi - p.song_lo;
-  const int blo = p.song_lo + tile * p.block_songs;
-  const int bw = min(p.song_hi, blo + p.block_songs) - blo;
-  if (s0 >= bw) return;  // (block-uniform) the last tile is partial: no such sub-range
-  const int sw = min(p.sub, bw - s0);
-  const int* toff_t = p.toff + (size_t)tile * p.n_tr;
+  if (s0 >= g.bw) return;  // (block-uniform) the last tile is partial: no such sub-range
+  const int* toff_t = p.toff + (size_t)g.tile * p.n_tr;
   for (int i = tid; i < sw; i += NT) us_acc[i] = 0ull;
   __syncthreads();
-
-  auto add = [&](int x, unsigned long long key) {
-    const unsigned loc = (unsigned)(x - s0);
-    if (loc < (unsigned)sw)  // result unused: a 64-bit LDS add without return
-      (void)__hip_atomic_fetch_add(&us_acc[loc], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
 
   for (int c = 0; c < p.n_chunks; ++c) {  // the written prefix of every chunk's list
     const int n = p.nbr_cnt[(size_t)bu * p.n_chunks + c];
@@ -204,15 +185,12 @@ __global__ __launch_bounds__(kUsThreads) void k_uasym_score(UsParams p) {
       const unsigned long long key = (unsigned long long)lk[i];
       if (key == 0ull) continue;  // a weight below 2^-(F+1): contributes nothing
       const int v = lv[i];
-      const int a = toff_t[v], b = toff_t[v + 1];
-      for (int x0 = a; x0 < b; x0 += kUsSeg) {
-        int st[kUsSeg];
-#pragma unroll
-        for (int j = 0; j < kUsSeg; ++j) st[j] = x0 + j < b ? (int)p.tsongs[x0 + j] : -1;
-#pragma unroll
-        for (int j = 0; j < kUsSeg; ++j)
-          if (st[j] >= 0) add(st[j], key);
-      }
+      // the neighbour's row of the tile, un-pipelined (csrc/mr_tile_walk.h)
+      walk_tile_row<kUsSeg>(toff_t[v], toff_t[v + 1], p.tsongs, [&](unsigned x) {
+        const unsigned loc = x - (unsigned)s0;
+        if (loc < (unsigned)sw)  // result unused: a 64-bit LDS add without return
+          (void)__hip_atomic_fetch_add(&us_acc[loc], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      });
     }
   }
   __syncthreads();
@@ -220,37 +198,15 @@ __global__ __launch_bounds__(kUsThreads) void k_uasym_score(UsParams p) {
   // the heard songs of this sub-range
   const long long t0 = p.te_off[u], t1 = p.te_off[u + 1];
   for (long long i = t0 + tid; i < t1; i += NT) {
-    const unsigned loc = (unsigned)(p.te_songs[i] - (blo + s0));
+    const unsigned loc = (unsigned)(p.te_songs[i] - (g.blo + s0));
     if (loc < (unsigned)sw) us_acc[loc] = kHeard;
   }
   __syncthreads();
-  const size_t o = (size_t)u * (size_t)width + (size_t)(blo + s0 - p.song_lo);
+  const size_t o = (size_t)u * (size_t)width + (size_t)(g.blo + s0 - p.song_lo);
   for (int i = tid; i < sw; i += NT) {
     const unsigned long long a = us_acc[i];
-    const double score = (double)(long long)a * p.inv_f;
-    if (p.f64)
-      static_cast<double*>(p.out)[o + i] = a == kHeard ? __longlong_as_double(0x7FF8000000000000ll) : score;
-    else
-      static_cast<float*>(p.out)[o + i] = a == kHeard ? __int_as_float(0x7FC00000) : (float)score;
+    store_model_value(p.out, p.f64, o + i, a == kHeard, (double)(long long)a * p.inv_f);
   }
-}
-
-template <typename T>
-struct Tmp {  // scratch device buffer of one call, stream-ordered
-  T* p = nullptr;
-  hipStream_t st = nullptr;
-  ~Tmp() { if (p) (void)hipFreeAsync(p, st); }
-};
-
-struct Drain {  // the call's host tables outlive their copies on every return path
-  hipStream_t st = nullptr;
-  ~Drain() { (void)hipStreamSynchronize(st); }
-};
-
-// A diagnostic setting MR_UASYM_*=n clamped to [lo, hi]; hi when unset.
-int env_clamped(const char* name, int lo, int hi) {
-  const char* e = std::getenv(name);
-  return e ? std::min(hi, std::max(lo, std::atoi(e))) : hi;
 }
 
 }  // namespace
@@ -259,23 +215,21 @@ extern "C" {
 
 int mr_ubm_asym_device(mr_ctx* ctx, double alpha, int32_t q, int32_t frac_bits, void* dense_dev) {
   if (!ctx) return fail(MR_E_INVALID, "null context");
-  if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(MR_E_INVALID, "alpha=%g must be in [0,1]", alpha);
-  if (q < 1 || q > MR_ASYM_MAX_Q) return fail(MR_E_INVALID, "q=%d must be in [1,%d]", q, MR_ASYM_MAX_Q);
+  int rc = mr_hip::check_asym_args(alpha, q);
+  if (rc) return rc;
   if (frac_bits != 0 && (frac_bits < 8 || frac_bits > 52))
     return fail(MR_E_INVALID, "frac_bits=%d must be 0 (the context's) or in [8,52]", frac_bits);
   if (!dense_dev) return fail(MR_E_INVALID, "null dense_dev");
-  mr_internal::UasymTables t;
-  int rc = mr_internal::uasym_tables(ctx, &t);
-  if (rc) return rc;
-  const mr_internal::SimilarTables& s = t.asym.sim;
+  mr_internal::ShardTables t;
+  if ((rc = mr_internal::shard_tables(ctx, "asymmetric user-based model", &t))) return rc;
   const int F = frac_bits ? frac_bits : t.frac_bits;
   int bits = 0;  // ceil(log2(max c_tr + 1)): the sum of max c_tr keys of at most about 2^F each stays in int64
   while ((1ll << bits) < (long long)t.max_ctr + 1) ++bits;
   if (F + bits > 62)
     return fail(MR_E_INVALID, "frac_bits=%d + %d bits for the largest train-listener count %d exceeds 62", F, bits,
                 t.max_ctr);
-  const int n_te = t.asym.n_te, n_tr = s.n_tr;
-  const int width = s.song_hi - s.song_lo;
+  const int n_te = t.n_te, n_tr = t.n_tr;
+  const int width = t.song_hi - t.song_lo;
   if (n_te <= 0 || width <= 0) return MR_OK;
 
   // pa = te_len^alpha, pb = tr_len^(1-alpha): the halves of two mr_asym_tables calls that are read
@@ -292,24 +246,21 @@ int mr_ubm_asym_device(mr_ctx* ctx, double alpha, int32_t q, int32_t frac_bits, 
   const size_t per_user = (size_t)std::max(1, n_tr) * 12 + (size_t)std::max(1, n_chunks) * 4;
   const int fit = (int)std::min<size_t>((size_t)n_te, std::max<size_t>(1, (size_t)MR_UASYM_SCRATCH_BYTES / per_user));
   const int batch = env_clamped("MR_UASYM_BATCH", 1, fit);
-  const int sub = std::min(s.block_songs, env_clamped("MR_UASYM_SUB", 64, kUasymMaxSub));
-  const int n_sub = (s.block_songs + sub - 1) / sub;
+  const int sub = std::min(t.block_songs, env_clamped("MR_UASYM_SUB", 64, kUasymMaxSub));
+  const int n_sub = (t.block_songs + sub - 1) / sub;
   const int rows = mr_internal::launch_rows(kUasymMaxBatch);  // (MR_LAUNCH_ROWS, diagnostic: fewer users per launch)
 
-  MR_HIP(hipSetDevice(s.device));
-  hipStream_t st = (hipStream_t)s.stream;
+  MR_HIP(hipSetDevice(t.device));
+  hipStream_t st = (hipStream_t)t.stream;
   Drain drain;
   drain.st = st;
   Tmp<double> d_a, d_b;
   Tmp<int> d_v, d_cnt;
   Tmp<long long> d_key;
-  d_a.st = d_b.st = d_v.st = d_cnt.st = d_key.st = st;
   const size_t slots = (size_t)batch * (size_t)std::max(1, n_tr);
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_a.p), pa.size() * 8, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_b.p), pb.size() * 8, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_v.p), slots * 4, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_key.p), slots * 8, st));
-  MR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_cnt.p), (size_t)batch * std::max(1, n_chunks) * 4, st));
+  if ((rc = d_a.alloc(pa.size(), st)) || (rc = d_b.alloc(pb.size(), st)) || (rc = d_v.alloc(slots, st)) ||
+      (rc = d_key.alloc(slots, st)) || (rc = d_cnt.alloc((size_t)batch * std::max(1, n_chunks), st)))
+    return rc;
   MR_HIP(hipMemcpyAsync(d_a.p, pa.data(), pa.size() * 8, hipMemcpyHostToDevice, st));
   MR_HIP(hipMemcpyAsync(d_b.p, pb.data(), pb.size() * 8, hipMemcpyHostToDevice, st));
 
@@ -317,16 +268,16 @@ int mr_ubm_asym_device(mr_ctx* ctx, double alpha, int32_t q, int32_t frac_bits, 
     const int nb = std::min(batch, n_te - u0);
     for (int r0 = 0; r0 < nb && n_chunks > 0; r0 += rows) {
       const int nr = std::min(rows, nb - r0);
-      UwParams wp{n_tr,      chunk,       n_chunks, q,     u0,    r0,      std::ldexp(1.0, F), t.asym.te_off, t.asym.te_songs,
-                  s.trs_off, s.trs_users, d_a.p,    d_b.p, d_v.p, d_key.p, d_cnt.p};
+      UwParams wp{n_tr,      chunk,       n_chunks, q,     u0,    r0,      std::ldexp(1.0, F), t.te_off, t.te_songs,
+                  t.trs_off, t.trs_users, d_a.p,    d_b.p, d_v.p, d_key.p, d_cnt.p};
       hipLaunchKernelGGL(k_uasym_weights, dim3(n_chunks, nr), dim3(kUwThreads), 0, st, wp);
       MR_HIP(hipGetLastError());
     }
     for (int r0 = 0; r0 < nb; r0 += rows) {
       const int nr = std::min(rows, nb - r0);
-      UsParams sp{n_tr,   s.song_lo, s.song_hi,     s.block_songs,   sub,   n_sub,   chunk,   n_chunks, t.asym.f64, u0, r0,
-                  std::ldexp(1.0, -F), s.toff, s.tsongs, t.asym.te_off, t.asym.te_songs, d_v.p, d_key.p, d_cnt.p, dense_dev};
-      hipLaunchKernelGGL(k_uasym_score, dim3(s.n_tiles * n_sub, nr), dim3(kUsThreads), 0, st, sp);
+      UsParams sp{n_tr,   t.song_lo, t.song_hi, t.block_songs, sub,      n_sub,      chunk, n_chunks, t.f64, u0,      r0,
+                  std::ldexp(1.0, -F), t.toff,    t.tsongs,      t.te_off, t.te_songs, d_v.p, d_key.p,  d_cnt.p, dense_dev};
+      hipLaunchKernelGGL(k_uasym_score, dim3(t.n_tiles * n_sub, nr), dim3(kUsThreads), 0, st, sp);
       MR_HIP(hipGetLastError());
     }
   }
