@@ -156,6 +156,13 @@ int mr_shard_info(const mr_ctx* ctx, int32_t* song_lo, int32_t* song_hi, int32_t
  * mr_options.stage1); songs per LDS tile and tiles per test user. */
 int mr_launch_info(const mr_ctx* ctx, int32_t* shape, int32_t* block_songs, int32_t* n_tiles);
 
+/* Fused shape after mr_load: threads per scoring workgroup (256, 512 or 1024;
+ * MR_FUSED_NT at load, 0 for the other shapes) and whether the lean fused
+ * kernel was picked (MR_FUSED_LEAN at load, and the load meets its launch-time
+ * conditions: walk schedule, threshold top-k, register merge, tiles of at
+ * most 1024 songs). Results do not depend on either. */
+int mr_fused_info(const mr_ctx* ctx, int32_t* threads, int32_t* lean);
+
 /* Test-user batch of the separate / wide shapes (mr_run launches the stage-1 and
  * scoring kernels once per batch of *batch users, sized so the neighbour lists
  * fit 8 GiB; = n_test_users for the other shapes) and the stage-1 chunking of

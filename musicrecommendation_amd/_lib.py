@@ -137,6 +137,7 @@ SIGNATURES = {
     "mr_load": (c_int, [c_void_p, POINTER(MrDataset)]),
     "mr_shard_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "mr_launch_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "mr_fused_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "mr_batch_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "mr_route_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
     "mr_topk_mode": (c_int, [c_void_p, POINTER(c_int32)]),

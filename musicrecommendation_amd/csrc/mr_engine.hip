@@ -131,7 +131,10 @@ __host__ __device__ inline int merge_lists_per_pass(int k);
 // candidate lists for the in-launch merge (stage_lists lists per pass), and
 // by the wide-tile top-k for its per-thread lists. n_chunks: separate shape's
 // stage-1 chunk count (prefix of the per-chunk neighbour counts).
-__host__ __device__ inline ScoreLds score_lds(int bs, int fused_ntr, int k, int n_tiles, int n_chunks = 0) {
+// nt: the workgroup's threads (the fused shape's NT; 256 otherwise).
+__host__ __device__ inline ScoreLds score_lds(int bs, int fused_ntr, int k, int n_tiles, int n_chunks = 0,
+                                              int nt = kThreads) {
+  const int nw = nt / 64;
   ScoreLds L;
   const int fused = fused_ntr > 0 ? 1 : 0;
   const int kk = k > 0 ? k : 1;
@@ -139,22 +142,22 @@ __host__ __device__ inline ScoreLds score_lds(int bs, int fused_ntr, int k, int 
   L.stage_lists = (k > 0 && n_tiles > 1) ? (n_tiles < per ? n_tiles : per) : 0;
   int a_bytes = bs * 8 + fused_ntr * 8;
   const int st_bytes = L.stage_lists * kk * 8 + align16(L.stage_lists * kk * 4);
-  const int wide_bytes = (k > 0 && bs > kMaxTopkTile) ? kThreads * kk * 8 + kThreads * kk * 4 : 0;
+  const int wide_bytes = (k > 0 && bs > kMaxTopkTile) ? 256 * kk * 8 + 256 * kk * 4 : 0;  // kWideLists lists
   if (wide_bytes > a_bytes) a_bytes = wide_bytes;
   int o = 0;
   L.acc = o; L.y = bs * 8; o = align16(a_bytes > st_bytes ? a_bytes : st_bytes);
   L.heard = o; o = align16(o + (bs / 32) * 4);
-  L.s_lo = o; o += fused * kThreads * 8;
-  L.s_w = o; o += fused * kThreads * 8;
-  L.s_pre = o; o = align16(o + (kThreads + 1) * 4);
-  L.s_scan = o; o = align16(o + kWaves * 4);
-  L.wk = o; o = align16(o + kWaves * kMaxTopK * 8);
-  L.ws = o; o = align16(o + kWaves * kMaxTopK * 4);
+  L.s_lo = o; o += fused * nt * 8;
+  L.s_w = o; o += fused * nt * 8;
+  L.s_pre = o; o = align16(o + (nt + 1) * 4);
+  L.s_scan = o; o = align16(o + nw * 4);
+  L.wk = o; o = align16(o + nw * kMaxTopK * 8);  // (>= 256 survivor slots: block_topk_threshold's cap)
+  L.ws = o; o = align16(o + nw * kMaxTopK * 4);
   L.fk = o; o = align16(o + kMaxTopK * 8);
   L.fs = o; o = align16(o + kMaxTopK * 4);
   L.flag = o; o = align16(o + 16);
   L.cpre = o; o = align16(o + (n_chunks > 0 ? (n_chunks + 1) * 4 : 0));
-  L.stg = o; o = align16(o + (n_chunks > 0 ? kWaves * kStgBytes : 0));
+  L.stg = o; o = align16(o + (n_chunks > 0 ? nw * kStgBytes : 0));
   L.gm = o; o = align16(o + kTopkScratch256);
   L.total = o;
   return L;
@@ -239,7 +242,8 @@ __host__ __device__ inline double ordered_value(unsigned long long k) {
   return x;
 }
 
-// Block-wide exclusive scan of one int per thread (256 threads). `sbuf` holds kWaves ints.
+// Block-wide exclusive scan of one int per thread (NT threads). `sbuf` holds NT / 64 ints.
+template <int NT = kThreads>
 __device__ __forceinline__ int block_excl_scan(int x, int* total, int* sbuf) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int incl = wave_incl_scan(x);
@@ -247,7 +251,7 @@ __device__ __forceinline__ int block_excl_scan(int x, int* total, int* sbuf) {
   __syncthreads();
   int off = 0, tot = 0;
 #pragma unroll
-  for (int i = 0; i < kWaves; ++i) {
+  for (int i = 0; i < NT / 64; ++i) {
     int s = sbuf[i];
     off += (i < w) ? s : 0;
     tot += s;
@@ -463,9 +467,10 @@ __device__ __forceinline__ void wave_merge_lists(int L, int k, const long long* 
 
 // Block top-k of n <= 1024 candidates get(i) into out (LDS). n <= 256: one
 // wave holds 4 per lane and selects alone; otherwise every wave selects from
-// its 256 (i = w*64 + lane + 256 j), then wave 0 merges the 4 sorted lists.
-// All threads call it; it ends with a barrier.
-template <typename Get>
+// its share (i = w*64 + lane + NT j, j < 4), then wave 0 merges the NT / 64
+// sorted lists (wk/ws: NT / 64 lists of k). All threads call it; it ends with
+// a barrier.
+template <int NT = kThreads, typename Get>
 __device__ __forceinline__ void block_topk(int n, int k, Get get, long long* wk, int* ws, long long* out_k,
                                            int* out_s) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -486,14 +491,14 @@ __device__ __forceinline__ void block_topk(int n, int k, Get get, long long* wk,
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int i = w * 64 + lane + kThreads * j;
+    const int i = w * 64 + lane + NT * j;
     rk[j] = kKeyNone;
     rs[j] = INT_MAX;
     if (i < n) get(i, rk[j], rs[j]);
   }
   wave_topk_regs<4>(rk, rs, k, wk + w * k, ws + w * k);
   __syncthreads();
-  if (w == 0) wave_merge_lists(kWaves, k, wk, ws, out_k, out_s);
+  if (w == 0) wave_merge_lists(NT / 64, k, wk, ws, out_k, out_s);
   __syncthreads();
 }
 
@@ -522,12 +527,15 @@ __device__ __forceinline__ void lane_list_insert(long long (&tk)[KS], int (&ts)[
   thr = nt;
 }
 
-// Block top-k (k <= kMaxTopkLarge) of n candidates get(i), any n: every thread
-// keeps a running list over i = tid + kThreads*j (ascending, so ties keep the
-// lower song), the 256 lists go to LDS (lk/ls: kThreads*k slots, may alias
-// the storage get() reads — a barrier separates them), each wave merges its
-// 64 lists, wave 0 merges the kWaves results. Ends with a barrier.
-template <typename Get>
+// Block top-k (k <= kMaxTopkLarge) of n candidates get(i), any n: each of the
+// block's first 256 threads (wider blocks keep 256 lists: the LDS they take
+// does not grow with NT) keeps a running list over i = tid + 256*j (ascending,
+// so ties keep the lower song), the 256 lists go to LDS (lk/ls: 256*k slots,
+// may alias the storage get() reads — a barrier separates them), each of the
+// first four waves merges its 64 lists, wave 0 merges the 4 results. Ends
+// with a barrier.
+constexpr int kWideLists = 256;
+template <int NT = kThreads, typename Get>
 __device__ __forceinline__ void block_topk_wide(int n, int k, Get get, long long* lk, int* ls, long long* wk,
                                                 int* ws, long long* out_k, int* out_s) {
   const int tid = threadIdx.x, w = tid >> 6;
@@ -536,20 +544,24 @@ __device__ __forceinline__ void block_topk_wide(int n, int k, Get get, long long
 #pragma unroll
   for (int t = 0; t < kMaxTopkLarge; ++t) { tk[t] = kKeyNone; ts[t] = INT_MAX; }
   long long thr = kKeyNone;
-  for (int i = tid; i < n; i += kThreads) {
-    long long key;
-    int song;
-    get(i, key, song);
-    if (key > thr) lane_list_insert(tk, ts, k, key, song, thr);
+  const bool lister = NT == kWideLists || tid < kWideLists;  // (wave-uniform)
+  if (lister)
+    for (int i = tid; i < n; i += kWideLists) {
+      long long key;
+      int song;
+      get(i, key, song);
+      if (key > thr) lane_list_insert(tk, ts, k, key, song, thr);
+    }
+  __syncthreads();
+  if (lister) {
+#pragma unroll
+    for (int t = 0; t < kMaxTopkLarge; ++t)
+      if (t < k) { lk[tid * k + t] = tk[t]; ls[tid * k + t] = tk[t] >= 0 ? ts[t] : -1; }
   }
   __syncthreads();
-#pragma unroll
-  for (int t = 0; t < kMaxTopkLarge; ++t)
-    if (t < k) { lk[tid * k + t] = tk[t]; ls[tid * k + t] = tk[t] >= 0 ? ts[t] : -1; }
+  if (lister) wave_merge_lists(64, k, lk + (size_t)w * 64 * k, ls + (size_t)w * 64 * k, wk + w * k, ws + w * k);
   __syncthreads();
-  wave_merge_lists(64, k, lk + (size_t)w * 64 * k, ls + (size_t)w * 64 * k, wk + w * k, ws + w * k);
-  __syncthreads();
-  if (w == 0) wave_merge_lists(kWaves, k, wk, ws, out_k, out_s);
+  if (w == 0) wave_merge_lists(kWideLists / 64, k, wk, ws, out_k, out_s);
   __syncthreads();
 }
 
@@ -649,11 +661,18 @@ constexpr int kRankU = NT <= 256 ? MR_RANK_UNROLL_FUSED : 1;  // the wide kernel
 // (key desc, song asc)): rank < k -> output slot; slots past nc get (-1, -1).
 // crank: 256 zeroed ints. All threads call it; it ends with a barrier (not
 // after the stores to a global dst).
-template <int NT>
+// FR: the fused shape at any NT keeps its 256-thread limits — the one-wave
+// hand-over past nc^2 > 16384 and kRankU<256> reads in flight. COLD (the lean
+// fused kernel): the one-wave select is marked unlikely, so its block is laid
+// out after the straight-line path. (As __noinline__ calls the lean kernel's
+// cold paths cost it the callee's register budget and a scratch frame: 248
+// VGPRs, 8-304 bytes of scratch per lane; profiles/fused_threads.)
+template <int NT, bool FR = false, bool COLD = false>
 __device__ __forceinline__ void rank_survivors(int nc, int k, const long long* ck, const int* cs, int* crank,
                                                long long* out_k, int* out_s, const TopkDst& dst = TopkDst{}) {
   const int tid = threadIdx.x, lane = tid & 63;
-  if (nc * nc > kRankQ<NT> * NT) {  // many ties at tau: one wave selects (4 candidates per lane)
+  const bool one_wave = FR ? nc * nc > kRankQ<256> * 256 : nc * nc > kRankQ<NT> * NT;
+  if (COLD ? __builtin_expect(one_wave, 0) : one_wave) {  // many ties at tau: one wave selects (4 candidates per lane)
     if (tid < 64) {
       long long rk[4];
       int rs[4];
@@ -684,7 +703,7 @@ __device__ __forceinline__ void rank_survivors(int nc, int k, const long long* c
       // keeps the LDS reads of kRankU of them in flight instead of one round
       // trip each — C1 10.47 -> 9.65 us per step at 4, 10.14 at 8,
       // profiles/r06/s51)
-      constexpr int U = kRankU<NT>;
+      constexpr int U = FR ? kRankU<256> : kRankU<NT>;
       if constexpr (U > 1) {
         for (; j + U <= je; j += U) {
           long long o[U];
@@ -775,8 +794,9 @@ __device__ __forceinline__ void block_tau(int k, long long mk, int ms, unsigned 
 
 // NG rows of NT / NG threads: more rows give a tighter tau (fewer survivors
 // to rank) for NG^2 / NT comparisons per thread.
-template <int NT, typename Get, int NG = NT / 16>
-__device__ __forceinline__ bool block_topk_threshold(int n, int k, Get get, long long mk, int ms, unsigned char* gm,
+// (FR, COLD: rank_survivors' fused-shape limits and cold one-wave select.)
+template <int NT, typename Get, int NG, bool FR, bool COLD>
+__device__ __forceinline__ bool block_topk_threshold_as(int n, int k, Get get, long long mk, int ms, unsigned char* gm,
                                                      long long* ck, int* cs, int cap, long long* out_k, int* out_s,
                                                      long long* sb = nullptr, const TopkDst& dst = TopkDst{}) {
   long long* gk = reinterpret_cast<long long*>(gm);
@@ -804,8 +824,14 @@ __device__ __forceinline__ bool block_topk_threshold(int n, int k, Get get, long
   stamp_at(sb, 11);
   const int nc = *counter;
   if (nc > cap) return false;
-  rank_survivors<NT>(nc, k, ck, cs, crank, out_k, out_s, dst);
+  rank_survivors<NT, FR, COLD>(nc, k, ck, cs, crank, out_k, out_s, dst);
   return true;
+}
+template <int NT, typename Get, int NG = NT / 16>
+__device__ __forceinline__ bool block_topk_threshold(int n, int k, Get get, long long mk, int ms, unsigned char* gm,
+                                                     long long* ck, int* cs, int cap, long long* out_k, int* out_s,
+                                                     long long* sb = nullptr, const TopkDst& dst = TopkDst{}) {
+  return block_topk_threshold_as<NT, Get, NG, false, false>(n, k, get, mk, ms, gm, ck, cs, cap, out_k, out_s, sb, dst);
 }
 
 constexpr int kMergeStageBytes = 32 * 1024;  // LDS staging of tile lists per merge pass
@@ -869,11 +895,11 @@ __device__ __forceinline__ long long lower_bound_user(const int* trs_users, long
 }
 
 // Accumulate Y[v] += w(s2) over v ∈ L_tr(s2), s2 ∈ T(u): a flattened walk over
-// the listener lists of T(u), 256 songs of T(u) at a time; add(v, w) performs
+// the listener lists of T(u), NT songs of T(u) at a time; add(v, w) performs
 // the (integer, order-independent) accumulation. mark(s2) is called once per
 // song of T(u) (heard-song bookkeeping). ranged: only listeners v in [v0, v1)
 // (a stage-1 chunk; the sorted lists are cut by binary search).
-template <int MODEL, typename Add, typename Mark>
+template <int MODEL, int NT = kThreads, typename Add, typename Mark>
 __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, const int* te_songs,
                                                 const long long* trs_off, const int* trs_users,
                                                 const long long* q_song, long long* s_lo, long long* s_w,
@@ -882,8 +908,8 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
                                                 int chunk_idx = 0, int nc1 = 0, const int2* te_rng = nullptr,
                                                 const long long* te_q = nullptr, long long* sb = nullptr) {
   const int tid = threadIdx.x;
-  for (long long base = t0; base < t1; base += kThreads) {
-    const int n = (int)min((long long)kThreads, t1 - base);
+  for (long long base = t0; base < t1; base += NT) {
+    const int n = (int)min((long long)NT, t1 - base);
     int len = 0;
     if (tid < n && te_rng && !ranged) {
       // listener range and weight of each song of T(u) resolved at load time
@@ -912,9 +938,9 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
       mark(s2);
     }
     int total;
-    const int pre = block_excl_scan(len, &total, s_scan);
+    const int pre = block_excl_scan<NT>(len, &total, s_scan);
     s_pre[tid] = pre;
-    if (tid == 0) s_pre[kThreads] = total;
+    if (tid == 0) s_pre[NT] = total;
     __syncthreads();
     stamp_at(sb, 10);  // (diagnostic build) the batch's songs resolved and scanned
     // 16 flattened entries per thread in flight: the listener loads of one
@@ -926,7 +952,7 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
     // of stage 1 for C2's heaviest user; 16-wide lockstep with fixed 8 steps
     // cost more than it saved.)
     const int nsteps = n > 1 ? 32 - __clz(n - 1) : 0;
-    for (int i0 = tid; i0 < total; i0 += 16 * kThreads) {
+    for (int i0 = tid; i0 < total; i0 += 16 * NT) {
       const int ib = i0 - tid;  // block-uniform
       int v[16];
       unsigned long long wv[16];
@@ -934,8 +960,8 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
       for (int r = 0; r < 16; ++r) { v[r] = -1; wv[r] = 0ull; }
 #pragma unroll
       for (int g2 = 0; g2 < 4; g2 += 2) {  // two groups of 4 at a time
-        if (ib + g2 * 4 * kThreads >= total) break;
-        if (ib + (g2 + 1) * 4 * kThreads < total) {
+        if (ib + g2 * 4 * NT >= total) break;
+        if (ib + (g2 + 1) * 4 * NT < total) {
           // both groups hold entries (heavy users): 8 searches in lockstep, so
           // the second group's LDS reads overlap the first's (C2's heaviest
           // user: stage 1 4.9 -> 4.5 us)
@@ -945,14 +971,14 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
           for (int st = 0; st < nsteps; ++st) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const int i = i0 + (g2 * 4 + e) * kThreads;
+              const int i = i0 + (g2 * 4 + e) * NT;
               const int m = (a[e] + b[e]) >> 1;
               if (s_pre[m] <= i) a[e] = m; else b[e] = m;
             }
           }
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            const int i = i0 + (g2 * 4 + e) * kThreads;
+            const int i = i0 + (g2 * 4 + e) * NT;
             if (i < total) {
               v[g2 * 4 + e] = trs_users[s_lo[a[e]] + (i - s_pre[a[e]])];
               wv[g2 * 4 + e] = (unsigned long long)s_w[a[e]];
@@ -967,14 +993,14 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
         for (int st = 0; st < nsteps; ++st) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const int i = i0 + (g * 4 + e) * kThreads;
+            const int i = i0 + (g * 4 + e) * NT;
             const int m = (a[e] + b[e]) >> 1;
             if (s_pre[m] <= i) a[e] = m; else b[e] = m;  // size 1: m = a, stays
           }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int i = i0 + (g * 4 + e) * kThreads;
+          const int i = i0 + (g * 4 + e) * NT;
           if (i < total) {
             v[g * 4 + e] = trs_users[s_lo[a[e]] + (i - s_pre[a[e]])];
             wv[g * 4 + e] = (unsigned long long)s_w[a[e]];
@@ -991,7 +1017,7 @@ __device__ __forceinline__ void walk_neighbours(long long t0, long long t1, cons
 }
 
 // Y indexed by v - v0 (v0 = 0 unless ranged).
-template <int MODEL>
+template <int MODEL, int NT = kThreads>
 __device__ __forceinline__ void accumulate_neighbours(unsigned long long* Y, long long t0, long long t1,
                                                       const int* te_songs, const long long* trs_off,
                                                       const int* trs_users, const long long* q_song,
@@ -1000,7 +1026,7 @@ __device__ __forceinline__ void accumulate_neighbours(unsigned long long* Y, lon
                                                       int v0 = 0, int v1 = 0, const int* sbound = nullptr,
                                                       int chunk_idx = 0, int nc1 = 0, const int2* te_rng = nullptr,
                                                       const long long* te_q = nullptr, long long* sb = nullptr) {
-  walk_neighbours<MODEL>(
+  walk_neighbours<MODEL, NT>(
       t0, t1, te_songs, trs_off, trs_users, q_song, s_lo, s_w, s_pre, s_scan,
       [&](int v, unsigned long long w) { atomicAdd(&Y[v - v0], w); },
       [&](int s2) {
@@ -1089,6 +1115,14 @@ __global__ __launch_bounds__(kThreads) void k_neighbours(NbrParams p) {
 #define MR_SCHED_SE 8     // fused stage 1: schedule entries per thread per batch (C2 per step: 4 9.92-10.00,
                           // 6 10.26-10.33, 8 9.93-9.95, 12 10.27-10.30, 16 10.99-11.02 us; profiles/r06/s33-s34)
 #endif
+// The fused kernel's per-thread counts at NT threads: MR_SCHED_SE and
+// kFusedPre are the 256-thread figures, and one batch keeps covering the same
+// 2048 schedule entries / 1024 tile entries and songs at any NT.
+constexpr int sched_se(int nt) { return MR_SCHED_SE * 256 / nt > 1 ? MR_SCHED_SE * 256 / nt : 1; }
+constexpr int fused_pre(int nt) { return kFusedPre * 256 / nt > 1 ? kFusedPre * 256 / nt : 1; }
+// Survivor slots of the fused threshold top-k (block_topk_threshold's cap, its
+// crank array): the same at every NT.
+constexpr int kFusedCap = 256;
 #ifndef MR_COUNTER_STRIDE
 #define MR_COUNTER_STRIDE 64  // words between two users' hand-off counters: one 256-B line each.
                               // Every tile's agent-scope add on its user's counter is a memory-side
@@ -1156,11 +1190,96 @@ struct ScoreParams {
   const float* rsq_c;
 };
 
-template <int MODEL, typename OutT, bool FUSED>
-__global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
+// The in-launch merge through LDS: the tiles' sorted candidate lists are
+// staged into mk/ms with sc1 loads (stage_lists lists per pass; the running
+// top-k is list 0 of every later pass), one pass of all lists tries the
+// threshold select, otherwise wave 0 runs the tournament. Returns whether the
+// select wrote the user's outputs (top_key/top_song/top_score, the user's
+// rows) itself; else the result is in fk/fs. All threads call it.
+template <int NT>
+__device__ __forceinline__ bool merge_staged(int n_tiles, int k, int merge_rows, int topk_lists, int stage_lists,
+                                             const long long* ck, const int* cs, long long* mk, int* ms,
+                                             unsigned char* gm, long long* wk, int* ws, long long* fk, int* fs,
+                                             long long* top_key, int* top_song, double* top_score, long long* sb) {
+  const int tid = threadIdx.x, w = tid >> 6;
+  int done = 0, off = 0;
+  bool merged_direct = false;
+  while (done < n_tiles) {
+    const int nl = min(n_tiles - done, stage_lists - off);
+    // 4 candidates per thread in flight per batch (loads first, then LDS)
+    for (int i0 = tid; i0 < nl * k; i0 += 4 * NT) {
+      long long lk4[4];
+      int ls4[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = i0 + r * NT;
+        lk4[r] = kKeyNone;
+        ls4[r] = -1;
+        if (i < nl * k) {
+          lk4[r] = ld_sc1(&ck[(size_t)done * k + i]);
+          ls4[r] = ld_sc1(&cs[(size_t)done * k + i]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = i0 + r * NT;
+        if (i < nl * k) {
+          mk[off * k + i] = lk4[r];
+          ms[off * k + i] = ls4[r];
+        }
+      }
+    }
+    for (int i = tid; i < off * k; i += NT) {
+      mk[i] = fk[i];
+      ms[i] = fs[i];
+    }
+    __syncthreads();
+    stamp_at(sb, 6);
+    bool merged = false;
+    TopkDst mdst;  // the user's outputs, written by the ranking threads
+#ifndef MR_TOPK_VIA_LDS
+    mdst.key = top_key;
+    mdst.song = top_song;
+    mdst.score = top_score;
+#endif
+    // (A threshold on the sorted lists' HEADS — the k-th best head — measured
+    // 16.7 vs 14.0 us per C2 step: it is a much looser bound than the row
+    // bests, ~5x the survivors to rank; profiles/r02/c2_merge_heads_ab.txt.)
+    if (!topk_lists && done == 0 && nl == n_tiles && k <= NT / 16) {  // one pass: threshold select
+      auto get_c = [&](int i, long long& key, int& song) { key = mk[i]; song = ms[i]; };
+      long long bk;
+      int bsg;
+      thread_best<NT>(nl * k, get_c, bk, bsg);
+      if (merge_rows == 16)
+        merged = block_topk_threshold_as<NT, decltype(get_c), 16, true, false>(nl * k, k, get_c, bk, bsg, gm,
+                                                                    wk, ws, kFusedCap, fk, fs, nullptr, mdst);
+      else if (merge_rows == 64)
+        merged = block_topk_threshold_as<NT, decltype(get_c), 64, true, false>(nl * k, k, get_c, bk, bsg, gm,
+                                                                    wk, ws, kFusedCap, fk, fs, nullptr, mdst);
+      else
+        merged = block_topk_threshold_as<NT, decltype(get_c), 32, true, false>(nl * k, k, get_c, bk, bsg, gm,
+                                                                    wk, ws, kFusedCap, fk, fs, nullptr, mdst);
+    }
+    if (!merged) {
+      if (w == 0) wave_merge_lists(nl + off, k, mk, ms, fk, fs);
+      __syncthreads();
+    }
+    stamp_at(sb, 8);
+    merged_direct = merged && mdst.key;
+    done += nl;
+    off = 1;
+  }
+  return merged_direct;
+}
+template <int MODEL, typename OutT, bool FUSED, int NT = kThreads, bool LEAN = false>
+__global__ __launch_bounds__(NT) void k_score(ScoreParams p) {
+  static_assert(NT == 256 || NT == 512 || NT == 1024, "workgroup of 4, 8 or 16 waves");
+  static_assert(FUSED || (NT == kThreads && !LEAN), "the separate shape keeps 256 threads");
+  constexpr int NW = NT / 64;
+  constexpr int kPre = fused_pre(NT);
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int bs = p.block_songs;
-  const ScoreLds L = score_lds(bs, FUSED ? p.n_tr : 0, p.topk, p.n_tiles, FUSED ? 0 : p.n_chunks);
+  const ScoreLds L = score_lds(bs, FUSED ? p.n_tr : 0, p.topk, p.n_tiles, FUSED ? 0 : p.n_chunks, NT);
   unsigned long long* acc = reinterpret_cast<unsigned long long*>(smem_raw + L.acc);
   unsigned* heard = reinterpret_cast<unsigned*>(smem_raw + L.heard);
   long long* wk = reinterpret_cast<long long*>(smem_raw + L.wk);
@@ -1192,8 +1311,8 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
 #endif
   MR_STAMP(0);
 
-  for (int i = tid; i < bw; i += kThreads) acc[i] = 0ull;
-  for (int i = tid; i < bs / 32; i += kThreads) heard[i] = 0u;
+  for (int i = tid; i < bw; i += NT) acc[i] = 0ull;
+  for (int i = tid; i < bs / 32; i += NT) heard[i] = 0u;
   const long long t0 = p.te_off[u], t1 = p.te_off[u + 1];
   // Fused stage 1 from the walk schedule: its first loads (this thread's
   // first song of T(u) for the heard bitmap, its first kSE schedule entries)
@@ -1202,8 +1321,9 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
   // the prefetches issued after them. (Unconditional loads at clamped
   // indices, validity re-derived from the index at use: a predicated load
   // compiles to a branch with a full wait.)
-  const bool sched = FUSED && p.te_sched != nullptr;
-  constexpr int kSE = MR_SCHED_SE;  // schedule entries per thread in flight
+  // (LEAN: the host launches it only with a schedule, see lean_ok)
+  const bool sched = LEAN || (FUSED && p.te_sched != nullptr);
+  constexpr int kSE = sched_se(NT);  // schedule entries per thread in flight
   long long se0 = 0, se1 = 0;
   int hs0 = -1;
   uint2 sc1[kSE];
@@ -1213,37 +1333,37 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
     if (t1 > t0) hs0 = p.te_songs[min(t0 + tid, t1 - 1)];  // (block-uniform guards: an empty user reads nothing)
     if (se1 > se0) {
 #pragma unroll
-      for (int r = 0; r < kSE; ++r) sc1[r] = p.te_sched[min(se0 + tid + (long long)r * kThreads, se1 - 1)];
+      for (int r = 0; r < kSE; ++r) sc1[r] = p.te_sched[min(se0 + tid + (long long)r * NT, se1 - 1)];
     }
   }
   // Prefetch this thread's epilogue scales (hidden behind stages 1-2): songs
-  // tid + 256 j of the tile, j < kFusedPre (the whole tile up to 1024 songs).
-  double sc[kFusedPre];
+  // tid + NT j of the tile, j < kPre (the whole tile up to 1024 songs).
+  double sc[kPre];
 #pragma unroll
-  for (int j = 0; j < kFusedPre; ++j) {
-    const int i = tid + j * kThreads;
+  for (int j = 0; j < kPre; ++j) {
+    const int i = tid + j * NT;
     sc[j] = (MODEL == MR_IBM && i < bw) ? p.sqrt_c[blo + i] : 1.0;
   }
 
   if (FUSED) {
     // Stage 2's inputs do not depend on the test user: the tile's entries
     // (train user, song) are one contiguous run of tpack (tile-major CSR), so
-    // they are loaded now, coalesced, 4 per thread, and land while stage 1
+    // they are loaded now, coalesced, kPre per thread (1024 per block), and land while stage 1
     // runs; stage 2 is then LDS work only (Y[v] lookups + atomics), balanced
     // over the block whatever the segment lengths. (The per-neighbour segment
     // walk it replaces waited on up to 3 dependent load batches for heavy
     // listeners: 3.0 us median, 4.3 us max per C2 tile.)
     const int e0 = p.toff[(size_t)tile * p.n_tr], e1 = p.toff[(size_t)(tile + 1) * p.n_tr];
-    unsigned pk[kFusedPre];
+    unsigned pk[kPre];
 #pragma unroll
-    for (int j = 0; j < kFusedPre; ++j) {
-      const int i = e0 + tid + j * kThreads;
+    for (int j = 0; j < kPre; ++j) {
+      const int i = e0 + tid + j * NT;
       pk[j] = i < e1 ? p.tpack[i] : 0xffffffffu;
     }
-    double str[kFusedPre];  // ubm: sqrt|S(v)| of this thread's first train users
+    double str[kPre];  // ubm: sqrt|S(v)| of this thread's first train users
 #pragma unroll
-    for (int r = 0; r < kFusedPre; ++r) {
-      const int v = tid + r * kThreads;
+    for (int r = 0; r < kPre; ++r) {
+      const int v = tid + r * NT;
       str[r] = (MODEL == MR_UBM && v < p.n_tr) ? p.sqrt_tr[v] : 1.0;
     }
     unsigned long long* Y = reinterpret_cast<unsigned long long*>(smem_raw + L.y);
@@ -1257,7 +1377,7 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
       }
     };
     const bool any = sched && se1 > se0;  // (block-uniform: a user without entries gathers nothing)
-    for (int i = tid; i < p.n_tr; i += kThreads) Y[i] = 0ull;
+    for (int i = tid; i < p.n_tr; i += NT) Y[i] = 0ull;
     __syncthreads();
     if (sched) {
       // Stage 1 from the walk schedule: every (song of T(u), listener) entry
@@ -1272,26 +1392,26 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
         if (s2 >= blo && s2 < bhi) atomicOr(&heard[(s2 - blo) >> 5], 1u << ((s2 - blo) & 31));
       };
       if (t0 + tid < t1) mark(hs0);
-      for (long long i = t0 + tid + kThreads; i < t1; i += kThreads) mark(p.te_songs[i]);  // |T(u)| > 256
+      for (long long i = t0 + tid + NT; i < t1; i += NT) mark(p.te_songs[i]);  // |T(u)| > NT
 #ifdef MR_STAMPS
       stamp_at(sb, 10);
 #endif
       for (long long i0 = se0 + tid; any;) {
 #pragma unroll
         for (int r = 0; r < kSE; ++r)
-          if (i0 + (long long)r * kThreads < se1) atomicAdd(&Y[v[r]], wv[r]);
-        i0 += (long long)kSE * kThreads;
-        if (i0 >= se1) break;  // (users with more than kSE x 256 entries: the next batch)
+          if (i0 + (long long)r * NT < se1) atomicAdd(&Y[v[r]], wv[r]);
+        i0 += (long long)kSE * NT;
+        if (i0 >= se1) break;  // (users with more than kSE x NT entries: the next batch)
 #pragma unroll
-        for (int r = 0; r < kSE; ++r) sc1[r] = p.te_sched[min(i0 + (long long)r * kThreads, se1 - 1)];
+        for (int r = 0; r < kSE; ++r) sc1[r] = p.te_sched[min(i0 + (long long)r * NT, se1 - 1)];
         gather();
       }
 #ifdef MR_STAMPS
       stamp_at(sb, 11);
 #endif
       __syncthreads();
-    } else
-    accumulate_neighbours<MODEL>(Y, t0, t1, p.te_songs, p.trs_off, p.trs_users, p.q_song,
+    } else if constexpr (!LEAN)
+    accumulate_neighbours<MODEL, NT>(Y, t0, t1, p.te_songs, p.trs_off, p.trs_users, p.q_song,
                                  reinterpret_cast<long long*>(smem_raw + L.s_lo),
                                  reinterpret_cast<long long*>(smem_raw + L.s_w),
                                  reinterpret_cast<int*>(smem_raw + L.s_pre),
@@ -1306,14 +1426,14 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
     MR_STAMP(1);
     if (MODEL == MR_UBM) {  // overlap counts -> fixed-point cosines (MR:142-148), in place
       const double rs_u = p.sqrt_te[u];
-      for (int v = tid, r = 0; v < p.n_tr; v += kThreads, ++r) {
+      for (int v = tid, r = 0; v < p.n_tr; v += NT, ++r) {
         const unsigned long long y = Y[v];
         if (y != 0ull) {
           double sv;
-          if (r < kFusedPre) {  // static register index: no scratch spill
+          if (r < kPre) {  // static register index: no scratch spill
             sv = str[0];
 #pragma unroll
-            for (int x = 1; x < kFusedPre; ++x) sv = r == x ? str[x] : sv;
+            for (int x = 1; x < kPre; ++x) sv = r == x ? str[x] : sv;
           } else {
             sv = p.sqrt_tr[v];
           }
@@ -1323,19 +1443,19 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
       __syncthreads();
     }
 #pragma unroll
-    for (int j = 0; j < kFusedPre; ++j) {
+    for (int j = 0; j < kPre; ++j) {
       if (pk[j] == 0xffffffffu) continue;
       const unsigned long long y = Y[pk[j] >> 16];
       if (y != 0ull) atomicAdd(&acc[pk[j] & 0xffffu], y);
     }
-    for (int i = e0 + tid + kFusedPre * kThreads; i < e1; i += kThreads) {  // tiles of > 1024 entries
+    for (int i = e0 + tid + kPre * NT; i < e1; i += NT) {  // tiles of > 1024 entries
       const unsigned e = p.tpack[i];
       const unsigned long long y = Y[e >> 16];
       if (y != 0ull) atomicAdd(&acc[e & 0xffffu], y);
     }
   } else {
     __syncthreads();
-    for (long long i = t0 + tid; i < t1; i += kThreads) {
+    for (long long i = t0 + tid; i < t1; i += NT) {
       const int s = p.te_songs[i];
       if (s >= blo && s < bhi) atomicOr(&heard[(s - blo) >> 5], 1u << ((s - blo) & 31));
     }
@@ -1345,7 +1465,7 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
     int* s_scan = reinterpret_cast<int*>(smem_raw + L.s_scan);
     const int nch = p.n_chunks;
     int cnt = 0;
-    for (int c0 = 0; c0 < nch; c0 += kThreads) {
+    for (int c0 = 0; c0 < nch; c0 += NT) {
       const int cc = c0 + tid;
       const int x = cc < nch ? p.nbr_cnt[(size_t)bu * nch + cc] : 0;
       int tot;
@@ -1400,7 +1520,7 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
         }
       }
     };
-    const int step = kWaves * kStgItems;
+    const int step = NW * kStgItems;
     int v0[R], a0[R], b0[R], v1[R], a1[R], b1[R], v2[R];
     unsigned long long q0[R], q1[R], q2[R];
     int k0 = w * kStgItems;
@@ -1464,8 +1584,8 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
   long long mk = kKeyNone;
   int ms = INT_MAX;
 #pragma unroll
-  for (int j = 0; j < kFusedPre; ++j) {
-    const int i = tid + j * kThreads;
+  for (int j = 0; j < kPre; ++j) {
+    const int i = tid + j * NT;
     if (i < bw) {
       const bool h = (heard[i >> 5] >> (i & 31)) & 1u;
       double score = (double)(long long)acc[i] * inv_f;
@@ -1476,7 +1596,8 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
       if (key > mk) { mk = key; ms = blo + i; }
     }
   }
-  for (int i = tid + kFusedPre * kThreads; i < bw; i += kThreads) {  // tiles wider than 1024 songs
+  if constexpr (!LEAN)
+  for (int i = tid + kPre * NT; i < bw; i += NT) {  // tiles wider than 1024 songs
     const bool h = (heard[i >> 5] >> (i & 31)) & 1u;
     double score = (double)(long long)acc[i] * inv_f;
     if (MODEL == MR_IBM) score = score / p.sqrt_c[blo + i];
@@ -1514,29 +1635,31 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
     tdst.sc1 = true;
   }
 #endif
-  if (!p.topk_lists && k <= kThreads / 16) {
+  if (LEAN || (!p.topk_lists && k <= NT / 16)) {
 #ifdef MR_STAMPS
     long long* sbt = sb ? sb + 3 : nullptr;  // sub-phase stamps in slots 12-14
 #else
     long long* sbt = nullptr;
 #endif
-    thr_done = block_topk_threshold<kThreads, decltype(get_key), MR_TILE_ROWS>(
-        bw, k, get_key, mk, ms, smem_raw + L.gm, wk, ws, kWaves * kMaxTopK, fk, fs, sbt, tdst);
+    thr_done = block_topk_threshold_as<NT, decltype(get_key), MR_TILE_ROWS, true, LEAN>(
+        bw, k, get_key, mk, ms, smem_raw + L.gm, wk, ws, kFusedCap, fk, fs, sbt, tdst);
   }
   const bool direct = thr_done && tdst.key;
-  if (thr_done) {
+  if (LEAN ? __builtin_expect(thr_done, 1) : thr_done) {
+  } else if constexpr (LEAN) {
+    block_topk<NT>(bw, k, get_key, wk, ws, fk, fs);  // (lean tiles: bs <= kMaxTopkTile)
   } else if (bs <= kMaxTopkTile) {
-    block_topk(bw, k, get_key, wk, ws, fk, fs);
+    block_topk<NT>(bw, k, get_key, wk, ws, fk, fs);
   } else {
     long long* lk = reinterpret_cast<long long*>(smem_raw + L.acc);
-    int* ls = reinterpret_cast<int*>(smem_raw + L.acc + kThreads * k * 8);
-    block_topk_wide(bw, k, get_key, lk, ls, wk, ws, fk, fs);
+    int* ls = reinterpret_cast<int*>(smem_raw + L.acc + kWideLists * k * 8);
+    block_topk_wide<NT>(bw, k, get_key, lk, ls, wk, ws, fk, fs);
   }
   MR_STAMP(4);
 
   if (p.n_tiles == 1) {  // the tile is the whole shard: publish directly
     if (!direct)
-      for (int r = tid; r < k; r += kThreads) {
+      for (int r = tid; r < k; r += NT) {
         const size_t o = (size_t)u * k + r;
         p.top_key[o] = fk[r];
         p.top_song[o] = fs[r];
@@ -1557,7 +1680,7 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
   // the XCD's whole L2 (≈1.7-6.5 us per the guide's price table) on every
   // tile's critical path — and adds nothing this protocol needs on gfx950.
   if (!direct)
-    for (int r = tid; r < k; r += kThreads) {
+    for (int r = tid; r < k; r += NT) {
       st_sc1(&ck[(size_t)tile * k + r], fk[r]);
       st_sc1(&cs[(size_t)tile * k + r], fs[r]);
     }
@@ -1585,15 +1708,13 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
   {
     long long* mk = reinterpret_cast<long long*>(smem_raw + L.acc);
     int* ms = reinterpret_cast<int*>(smem_raw + L.acc + L.stage_lists * k * 8);
-    const int w = tid >> 6;
-    int done = 0, off = 0;
     merged_direct = false;
 #ifndef MR_MERGE_VIA_LDS
-    // At most one candidate per thread (C2: 22 tiles x 10 <= 256): each thread
+    // At most one candidate per thread (C2: 22 tiles x 10 <= NT): each thread
     // loads its candidate into registers and the threshold select reads it
     // there — no LDS staging pass and barrier before the select.
     const int nck = p.n_tiles * k;
-    if (!p.topk_lists && nck <= kThreads && k <= kThreads / 16 && p.merge_rows == 32) {
+    if (LEAN || (!p.topk_lists && nck <= NT && k <= NT / 16 && p.merge_rows == 32)) {
       long long rk = kKeyNone;
       int rs = INT_MAX;
       if (tid < nck) {
@@ -1613,80 +1734,28 @@ __global__ __launch_bounds__(kThreads) void k_score(ScoreParams p) {
       mdst.key = p.top_key + (size_t)u * k;
       mdst.song = p.top_song + (size_t)u * k;
       mdst.score = p.top_score + (size_t)u * k;
-      merged_direct = block_topk_threshold<kThreads, decltype(get_r), 32>(
+      merged_direct = block_topk_threshold_as<NT, decltype(get_r), 32, true, LEAN>(
           nck, k, get_r, rk >= 0 ? rk : kKeyNone, rk >= 0 ? rs : INT_MAX, smem_raw + L.gm, wk, ws,
-          kWaves * kMaxTopK, fk, fs, nullptr, mdst);
+          kFusedCap, fk, fs, nullptr, mdst);
       MR_STAMP(8);
     }
 #endif
-    while (!merged_direct && done < p.n_tiles) {
-      const int nl = min(p.n_tiles - done, L.stage_lists - off);
-      // 4 candidates per thread in flight per batch (loads first, then LDS)
-      for (int i0 = tid; i0 < nl * k; i0 += 4 * kThreads) {
-        long long lk4[4];
-        int ls4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = i0 + r * kThreads;
-          lk4[r] = kKeyNone;
-          ls4[r] = -1;
-          if (i < nl * k) {
-            lk4[r] = ld_sc1(&ck[(size_t)done * k + i]);
-            ls4[r] = ld_sc1(&cs[(size_t)done * k + i]);
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = i0 + r * kThreads;
-          if (i < nl * k) {
-            mk[off * k + i] = lk4[r];
-            ms[off * k + i] = ls4[r];
-          }
-        }
-      }
-      for (int i = tid; i < off * k; i += kThreads) {
-        mk[i] = fk[i];
-        ms[i] = fs[i];
-      }
-      __syncthreads();
-      MR_STAMP(6);
-      bool merged = false;
-      TopkDst mdst;  // the user's outputs, written by the ranking threads
-#ifndef MR_TOPK_VIA_LDS
-      mdst.key = p.top_key + (size_t)u * k;
-      mdst.song = p.top_song + (size_t)u * k;
-      mdst.score = p.top_score + (size_t)u * k;
+    if (LEAN ? __builtin_expect(!merged_direct, 0) : !merged_direct) {
+#ifdef MR_STAMPS
+      long long* sbm = sb;
+#else
+      long long* sbm = nullptr;
 #endif
-      // (A threshold on the sorted lists' HEADS — the k-th best head — measured
-      // 16.7 vs 14.0 us per C2 step: it is a much looser bound than the row
-      // bests, ~5x the survivors to rank; profiles/r02/c2_merge_heads_ab.txt.)
-      if (!p.topk_lists && done == 0 && nl == p.n_tiles && k <= kThreads / 16) {  // one pass: threshold select
-        auto get_c = [&](int i, long long& key, int& song) { key = mk[i]; song = ms[i]; };
-        long long bk;
-        int bsg;
-        thread_best<kThreads>(nl * k, get_c, bk, bsg);
-        if (p.merge_rows == 16)
-          merged = block_topk_threshold<kThreads, decltype(get_c), 16>(nl * k, k, get_c, bk, bsg, smem_raw + L.gm,
-                                                                      wk, ws, kWaves * kMaxTopK, fk, fs, nullptr, mdst);
-        else if (p.merge_rows == 64)
-          merged = block_topk_threshold<kThreads, decltype(get_c), 64>(nl * k, k, get_c, bk, bsg, smem_raw + L.gm,
-                                                                      wk, ws, kWaves * kMaxTopK, fk, fs, nullptr, mdst);
-        else
-          merged = block_topk_threshold<kThreads, decltype(get_c), 32>(nl * k, k, get_c, bk, bsg, smem_raw + L.gm,
-                                                                      wk, ws, kWaves * kMaxTopK, fk, fs, nullptr, mdst);
-      }
-      if (!merged) {
-        if (w == 0) wave_merge_lists(nl + off, k, mk, ms, fk, fs);
-        __syncthreads();
-      }
-      MR_STAMP(8);
-      merged_direct = merged && mdst.key;
-      done += nl;
-      off = 1;
+      long long* tk = p.top_key + (size_t)u * k;
+      int* tsg = p.top_song + (size_t)u * k;
+      double* tsc = p.top_score + (size_t)u * k;
+      // (LEAN: 32 rows and no topk_lists are launch-time conditions)
+      merged_direct = merge_staged<NT>(p.n_tiles, k, LEAN ? 32 : p.merge_rows, LEAN ? 0 : p.topk_lists, L.stage_lists,
+                                       ck, cs, mk, ms, smem_raw + L.gm, wk, ws, fk, fs, tk, tsg, tsc, sbm);
     }
   }
   if (!merged_direct)
-    for (int r = tid; r < k; r += kThreads) {
+    for (int r = tid; r < k; r += NT) {
       const size_t o = (size_t)u * k + r;
       p.top_key[o] = fk[r];
       p.top_song[o] = fs[r];
@@ -3854,6 +3923,8 @@ struct mr_ctx {
   bool loaded = false;
   bool ran = false;
   bool fused = false;
+  int fused_nt = kThreads;   // fused shape: threads per workgroup (fused_nt_opt)
+  bool fused_lean = false;   // fused shape: the lean kernel was picked (lean_ok)
   int shape = kShapeSeparate;
   int last_model = -1;
   int n_tr = 0, n_te = 0, n_s = 0;
@@ -4067,6 +4138,32 @@ bool fused_sched_opt() {
   const char* e = std::getenv("MR_FUSED_SCHED");
   return MR_FUSED_SCHED && !(e && std::atoi(e) == 0);
 }
+// Threads per fused scoring workgroup: 512 for tiles wider than 512 songs,
+// else 256 — C2 (22 tiles of 768 songs) 9.18 us per step at 512 lean against
+// 9.72 at 256 lean and the parent's 10.27; C1 (19 tiles of 256 songs, half of
+// 512 threads without a song) 11.78 at 512 lean against 9.33 at 256 lean and
+// the parent's 10.03; 1024 threads lose everywhere (13.0 / 16.3): at C2 the
+// row bests over 32-thread rows and a merge whose 220 candidates fill fewer
+// than k rows (every candidate survives, one wave selects) cost more than the
+// shorter per-thread chains save (profiles/fused_threads/ab.txt, final/). Only those two widths were measured:
+// tiles of 512 and of 1024 songs were not, and 512-song tiles stay at 256
+// threads for that reason alone. MR_FUSED_NT=256 / 512 / 1024 overrides it
+// (A/B experiments and tests; read at each mr_load).
+#ifndef MR_FUSED_LEAN_DEFAULT
+#define MR_FUSED_LEAN_DEFAULT 1
+#endif
+int fused_nt_opt(int block_songs) {
+  const char* e = std::getenv("MR_FUSED_NT");
+  const int v = e ? std::atoi(e) : 0;
+  if (v == 256 || v == 512 || v == 1024) return v;
+  return block_songs > 512 ? 512 : 256;
+}
+// The lean fused kernel where its launch-time conditions hold (lean_ok):
+// MR_FUSED_LEAN=0 / 1 (read at each mr_load).
+bool fused_lean_opt() {
+  const char* e = std::getenv("MR_FUSED_LEAN");
+  return e ? std::atoi(e) != 0 : MR_FUSED_LEAN_DEFAULT != 0;
+}
 // Heavy u16 rows by tile groups (k_cooc_group, default) or per tile
 // (MR_COOC_GROUP=0: k_cooc_build<512, true>; A/B experiments and tests; read
 // at each mr_load).
@@ -4188,11 +4285,31 @@ int auto_block_songs(int width, int n_te, bool fused, int k, int n_tr) {
   return (int)std::max<long long>(256, std::min(bs, cover));
 }
 
+// The block-uniform choices the lean fused kernel (k_score<.., LEAN = true>)
+// takes at compile time: stage 1 from the walk schedule, the threshold tile
+// top-k (k <= its 32 rows and NT / 16), the register-resident merge of 32
+// rows (at most one candidate per thread), tiles that fit the per-thread
+// prefetch (<= 1024 songs, so no wide-tile top-k either). Anything else runs
+// the general instantiation.
+bool lean_ok(const mr_ctx* c, int nt, int bs, int k, int n_tiles) {
+  return c->fused && c->te_sched.p != nullptr && !c->opt.topk_lists && k >= 1 && k <= MR_TILE_ROWS &&
+         k <= nt / 16 && (long long)n_tiles * k <= nt && merge_rows_opt() == 32 && bs <= fused_pre(nt) * nt &&
+         bs <= kMaxTopkTile;
+}
+
+template <int MODEL, typename OutT>
+ScoreKernel fused_kernel(int nt, bool lean) {
+  if (nt == 1024) return lean ? k_score<MODEL, OutT, true, 1024, true> : k_score<MODEL, OutT, true, 1024, false>;
+  if (nt == 512) return lean ? k_score<MODEL, OutT, true, 512, true> : k_score<MODEL, OutT, true, 512, false>;
+  return lean ? k_score<MODEL, OutT, true, 256, true> : k_score<MODEL, OutT, true, 256, false>;
+}
+
 template <int MODEL>
 void pick_kernels(mr_ctx* c) {
   const bool f64 = c->opt.out_dtype == MR_OUT_F64;
   if (c->fused)
-    c->score_kernel[MODEL] = f64 ? k_score<MODEL, double, true> : k_score<MODEL, float, true>;
+    c->score_kernel[MODEL] = f64 ? fused_kernel<MODEL, double>(c->fused_nt, c->fused_lean)
+                                 : fused_kernel<MODEL, float>(c->fused_nt, c->fused_lean);
   else
     c->score_kernel[MODEL] = f64 ? k_score<MODEL, double, false> : k_score<MODEL, float, false>;
   if (c->shape == kShapeWide) {
@@ -5025,10 +5142,15 @@ int setup_kernels(mr_ctx* c, const LaunchPlan& lp, int n_tr) {
                  !(e && e[0] == '0');
   }
   c->wide_lds = wide ? (size_t)wide_lds<kWideThreads>(bs, k, n_chunks).total : 0;
+  c->fused_nt = fused ? fused_nt_opt(bs) : kThreads;
+  // (a wider workgroup's scan, survivor and wave-list regions take more LDS:
+  // a load that only fits with 256 threads keeps them)
+  if (fused && score_lds(bs, n_tr, k, lp.n_tiles, 0, c->fused_nt).total > kLdsBytes) c->fused_nt = kThreads;
+  c->fused_lean = fused && fused_lean_opt() && lean_ok(c, c->fused_nt, bs, k, lp.n_tiles);
   pick_kernels<MR_UBM>(c);
   pick_kernels<MR_IBM>(c);
   c->score_lds = wide ? c->wide_lds
-                      : (size_t)score_lds(bs, fused ? n_tr : 0, k, lp.n_tiles, fused ? 0 : n_chunks).total;
+                      : (size_t)score_lds(bs, fused ? n_tr : 0, k, lp.n_tiles, fused ? 0 : n_chunks, c->fused_nt).total;
   if (c->score_lds > 160 * 1024)
     return fail(MR_E_INVALID, "scoring kernel needs %zu B of LDS (> 160 KiB): lower block_songs or topk",
                 c->score_lds);
@@ -5353,6 +5475,14 @@ int mr_launch_info(const mr_ctx* c, int32_t* fused, int32_t* block_songs, int32_
   return MR_OK;
 }
 
+int mr_fused_info(const mr_ctx* c, int32_t* threads, int32_t* lean) {
+  if (!c) return fail(MR_E_INVALID, "null context");
+  if (!c->loaded) return fail(MR_E_STATE, "mr_fused_info before mr_load");
+  if (threads) *threads = c->fused ? c->fused_nt : 0;
+  if (lean) *lean = c->fused_lean ? 1 : 0;
+  return MR_OK;
+}
+
 int mr_batch_info(const mr_ctx* c, int32_t* batch, int32_t* chunk, int32_t* n_chunks) {
   if (!c) return fail(MR_E_INVALID, "null context");
   if (!c->loaded) return fail(MR_E_STATE, "mr_batch_info before mr_load");
@@ -5631,8 +5761,8 @@ int run_model(mr_ctx* c, int model) {
       sp.topk_lists = c->opt.topk_lists;
       if (c->mm_on && wide) { sp.mm_key = c->mm_key.p; sp.mm_n = c->n_te; }
       sp.cand = wide && c->cand_on && !sp.mm_key; sp.rsq_c = c->rsq_c.p;
-      hipLaunchKernelGGL(c->score_kernel[model], dim3(c->n_tiles, gy), dim3(wide ? kWideThreads : kThreads),
-                         c->score_lds, st, sp);
+      hipLaunchKernelGGL(c->score_kernel[model], dim3(c->n_tiles, gy),
+                         dim3(wide ? kWideThreads : c->fused ? c->fused_nt : kThreads), c->score_lds, st, sp);
       MR_HIP(hipGetLastError());
       if (wide && k > 0 && c->n_tiles > 1) {  // per-user top-k over the tiles' candidates
         MergeParams mp{c->n_tiles, k, k, (long long)c->n_tiles * k, (long long)k, (long long)k, c->cand_key.p, c->cand_song.p,

@@ -72,6 +72,10 @@ class Engine:
                    "mr_launch_info")
         self.shape = _lib.SHAPES[fz.value]
         self.fused, self.block_songs, self.n_tiles = self.shape == "fused", bsz.value, nt.value
+        fth, fln = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self._L.mr_fused_info(self._h, ctypes.byref(fth), ctypes.byref(fln)), "mr_fused_info")
+        # fused shape: threads per scoring workgroup (0 otherwise), and whether the lean kernel runs
+        self.fused_threads, self.fused_lean = fth.value, bool(fln.value)
         b, ch, nch = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self._L.mr_batch_info(self._h, ctypes.byref(b), ctypes.byref(ch), ctypes.byref(nch)),
                    "mr_batch_info")
