@@ -359,9 +359,19 @@ int mr_topk_merge_records_async(mr_ctx* ctx, int32_t n_shards, int32_t n_te, int
  * are indexed in the driver's sorted order (main.scala:57-59: user, then song,
  * heard songs skipped); pair_base = index of this context's first pair in the
  * full model (0 unless the context holds a block of test users), n_pairs = the
- * full model's length. All three are synchronous. */
+ * full model's length. All three are synchronous.
+ * The aggregation threshold is (int64_t)(param * (double)n_pairs), truncated
+ * to 64 bits, and pair indices are 64-bit throughout. The reference's
+ * (param * length).toInt (MR:371) has 32 bits: past 2^31 pairs (full scale:
+ * 3.85e9) it no longer holds the product (a JVM double-to-int conversion
+ * saturates at 2^31 - 1); below 2^31 pairs the two agree.
+ * Linear combines every element, a heard song's included (NaN in either model
+ * stays NaN; models from mr_run_into carry NaN there). Aggregation and
+ * stochastic store NaN at every heard song of the context's T(u) whatever the
+ * models hold there: a heard song is no pair (MR:109) and has no index. The
+ * sweep below forms the same values. */
 #define MR_COMB_LINEAR      0 /* getLinearCombinationModel MR:317-351: ubm*param + ibm*(1-param) */
-#define MR_COMB_AGGREGATION 1 /* getAggregationModel MR:361-418: pairs < (int)(param*n_pairs) from ibm */
+#define MR_COMB_AGGREGATION 1 /* getAggregationModel MR:361-418: pairs < (int64_t)(param*n_pairs) from ibm */
 #define MR_COMB_STOCHASTIC  2 /* getStochasticCombinationModel MR:429-481: ibm where u(seed,pair) < param;
                                  u = 24-bit uniform of splitmix64(seed + (idx+1)*0x9E3779B97F4A7C15) */
 int mr_combine_device(mr_ctx* ctx, int kind, double param, uint64_t seed, int64_t pair_base, int64_t n_pairs,

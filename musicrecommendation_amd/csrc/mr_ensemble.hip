@@ -330,7 +330,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_pred(EvalParams p) {
   const OutT* d = reinterpret_cast<const OutT*>(p.dense);
   OutT xt[kThresholds];
 #pragma unroll
-  for (int t = 0; t < kThresholds; ++t)  // unused slots: +inf, never reached
+  for (int t = 0; t < kThresholds; ++t)  // unused slots: +inf, reached by a +inf score only; never stored
     xt[t] = t < p.n_thr ? (sizeof(OutT) == 4 ? (OutT)p.xt_f[t] : (OutT)p.xt_d[t]) : (OutT)INFINITY;
   int cnt[kThresholds];
 #pragma unroll
@@ -352,8 +352,8 @@ __global__ __launch_bounds__(kThreads) void k_eval_pred(EvalParams p) {
     return;
   }
 #pragma unroll
-  for (int t = 0; t < kThresholds; ++t)
-    if (cnt[t]) atomicAdd(&p.pred[(size_t)i * p.n_thr + t], cnt[t]);
+  for (int t = 0; t < kThresholds; ++t)  // t < n_thr: a +inf score passes the unused slots' +inf
+    if (t < p.n_thr && cnt[t]) atomicAdd(&p.pred[(size_t)i * p.n_thr + t], cnt[t]);
 }
 
 template <typename OutT>
